@@ -1,12 +1,22 @@
 #!/usr/bin/env python3
 """Benchmarks of the hot path on MI355X, one JSON line per run (rank 0).
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what its headline needs: set-up, warm-up, the K timed steps
+of the selected configuration and the line — `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall-clock
+milliseconds of one timed step), the `roofline` of that timed region and `summary`.  Everything else the line can carry (the
+sub-objects of other configurations, layouts and in-place runs, `integrity`, per-launch and copy-bandwidth probes,
+`cpu_baseline`, `perf_guard`) takes runs of its own and is measured only with --full.
+
+--dump-outputs DIR: after the timed steps, what the last one handed its caller — y and the written-back state — goes to
+DIR/*.npy (dump_outputs() below).  The timed steps start from the stream's initial state, so these arrays depend on the
+arguments alone, not on how many untimed steps the clocks took to settle.
+
 --config c2 (default; BASELINE.json configs[1], SURVEY.md §8d "C2", the headline metric):
     i32 DF1 biquad, 65536 lanes x 4096 samples per lane, shared Q30 coefficients,
     `idsp_biquad_i32_df1` on a FRAME_MAJOR `[[i32; 65536]; 4096]` tensor (1 GiB in, 1 GiB out).
     With --gpus N every rank runs this per-GPU workload on its own lanes (WEAK scaling).
-    The line also carries a `c5` sub-object (below) so that one command yields both scaling curves.
-    Beside `c5` the default line carries `c3` and `c4` sub-objects: the other two single-GPU configurations of BASELINE.json,
+    With --full the line also carries a `c5` sub-object (below) so that one command yields both scaling curves.
+    Beside `c5` the --full line carries `c3` and `c4` sub-objects: the other two single-GPU configurations of BASELINE.json,
     each with its own timed region (<= 20 steps), `roofline` and `integrity`, so that one driver run measures all four.
 --config c3 (BASELINE.json configs[2], "C3"):
     hbf::HbfDec /16 (HBF_TAPS stages 3,2,1,0; src/hbf.rs:385-421), f32, 16384 lanes x 65536 input samples per lane
@@ -28,8 +38,8 @@ over gloo — a control-flow check, said so in the line (`ranks_share_device`). 
 result of a 1-int SUM all-reduce over the process group; `rccl_ranks` repeats it only when that group is an RCCL
 communicator (null over gloo and for a single process without a group).
 
-The default line also carries `inplace` sub-objects (C2 and C5 with y == x: `SplitInplace::inplace`,
-dsp-process/src/process.rs:135-142, the mode the reference itself benchmarks) and ends with a compact `summary`
+The --full line also carries `inplace` sub-objects (C2 and C5 with y == x: `SplitInplace::inplace`,
+dsp-process/src/process.rs:135-142, the mode the reference itself benchmarks).  Every line ends with a compact `summary`
 ({config: [ms per step, roofline fraction, integrity match]}) as its LAST key.
 
 A step = one pass of the hot path over the rank's batch, state carried from step to step like
@@ -43,10 +53,10 @@ Timing: W untimed warm-up steps, then further untimed steps until --settle-ms of
 synchronize pairs; `value` comes from that wall-clock interval (max over ranks).  The K launches are also
 bracketed by ONE pair of HIP events on the launch stream: `roofline` prices that interval / K — the average
 launch duration over the timed region — against HBM (8 B of algorithmic traffic per sample + the state
-planes once each way); per-launch median / min come from further launches with their own event pairs,
-after the timed region.  x and y are two plain, separate allocations.
+planes once each way); with --full, per-launch median / min come from further launches with their own event
+pairs, after the timed region.  x and y are two plain, separate allocations.
 
-Integrity (`integrity`): after the timed region every rank zeroes its state, runs ONE more step and sums
+Integrity (`integrity`, --full): after the timed region every rank zeroes its state, runs ONE more step and sums
 the 32-bit words of its output and of its written-back state (wrapping 64-bit sums).  The y sums meet in
 `sharding.allreduce_checksum`; every rank's pair is compared with the CPU oracle's value for that rank's
 input (tests/golden/bench_checksums.json, made by tests/golden/make_bench_checksums.py) and — at N = 1 —
@@ -57,7 +67,7 @@ on rank 0 (`default_rng([2, r])` on rank r > 0).  C5: a counter hash of (frame, 
 the device (`c5_input`), uniform in [-1, 1) — the 2^32-sample tensor is then the same whatever the number of
 ranks, which is what lets the strong-scaling checksums be compared across N.
 
-`cpu_baseline` times the CPU oracle (a C port of the reference's scalar loops — the reference is Rust and
+`cpu_baseline` (--full) times the CPU oracle (a C port of the reference's scalar loops — the reference is Rust and
 cannot be built here; the GPU box has no cargo / rustc either, profiles/r03_toolchain.txt) on the host cores of the
 same box: pinned POSIX threads inside the C library over contiguous lane blocks, both layouts, with as many threads
 as the container's CPU quota allows (`cores`) and with one thread.
@@ -497,6 +507,19 @@ class HipEngine:
             out.append(checksum_i64(yv.contiguous()))
         return out
 
+    def outputs(self, lane_idx):
+        """The lanes `lane_idx` of y ([frame][lane], x2 for Complex<i32>) and of the state words ([word][lane], uint32), on the host."""
+        import numpy as np
+
+        self.sync()
+        idx = self.torch.as_tensor(lane_idx, dtype=self.torch.int64, device=self.dev)
+        if self.frame_major:
+            y = self.y.view(self.frames, self.lanes, -1).index_select(1, idx)
+        else:
+            y = self.y.view(self.lanes, self.frames, -1).index_select(0, idx).transpose(0, 1)
+        y = y.cpu().numpy()
+        return (y[..., 0] if y.shape[-1] == 1 else y), self.state.index_select(1, idx).cpu().numpy().view(np.uint32)
+
     def kernel_name(self) -> str:
         return self.fn["last_kernel"]().decode(errors="replace")
 
@@ -523,6 +546,10 @@ def run_timed(engine, steps: int, warmup: int, settle_ms: float, dist=None):
             engine.step()
         done += 8
         engine.sync()
+    if hasattr(engine, "reset_state"):
+        # the timed steps start the stream afresh: what they compute depends on the arguments alone, not on how many
+        # untimed steps the clocks took to settle (--dump-outputs)
+        engine.reset_state()
     # barrier, synchronize, THEN the clock; after the K steps synchronize, read the clock, THEN the closing barrier: the
     # interval holds this rank's K steps only (the MAX over the ranks is taken by the caller), not the rendezvous
     if dist:
@@ -777,6 +804,29 @@ def summary_of(line: dict, head: str) -> dict:
     return out
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this much in all; larger outputs are dumped as a fixed lane sample
+
+
+def dump_outputs(engine, cfg: dict, out_dir: str):
+    """--dump-outputs (rank 0): what the last timed step handed its caller.  DIR/y.npy = y as [frame][lane] (x2 for the lock-in's
+    Complex<i32>), f32 outputs as float32 and i32 outputs as float64 (exact); DIR/state.npy = the written-back state as
+    [word][lane], each 32-bit word as an unsigned integer in float64 (exact); DIR/lanes.npy = the lanes both hold.  Where all
+    lanes would exceed DUMP_BYTES, the lanes are a sample drawn by numpy.random.default_rng(0) and sorted: the same for the
+    same arguments."""
+    import numpy as np
+
+    lanes, frames = engine.lanes, engine.frames
+    width = 2 if cfg.get("family") == "lockin" else 1
+    per_lane = 8 * (frames * width + cfg["state_words"] + 1)  # bytes, every value counted as 8
+    n = min(lanes, DUMP_BYTES // per_lane)
+    idx = np.arange(lanes) if n == lanes else np.sort(np.random.default_rng(0).choice(lanes, n, replace=False))
+    y, state = engine.outputs(idx)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy"), y.astype(np.float32 if y.dtype == np.float32 else np.float64))
+    np.save(os.path.join(out_dir, "state.npy"), state.astype(np.float64))
+    np.save(os.path.join(out_dir, "lanes.npy"), idx.astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------- ranks
 
 def free_port() -> int:
@@ -822,9 +872,10 @@ def gather_ints(values, dist, device):
 
 
 def run_config(cfg_name, args, engine_factory, dist, rank, world, local, backend, steps, warmup, settle_ms, lanes_override,
-               frames_override, inplace=False):
-    """One configuration on this rank: build the engine, the timed region, the reductions and the integrity
-    step.  Returns (line or None on ranks > 0, engine) — the caller frees the engine."""
+               frames_override, inplace=False, full=True, dump_dir=None):
+    """One configuration on this rank: build the engine, the timed region, the outputs to `dump_dir` (rank 0), the reductions
+    and — if `full` — the per-launch and copy probes and the integrity step.  Returns (line or None on ranks > 0, engine) — the
+    caller frees the engine."""
     import torch
 
     from idsp_amd.sharding import allreduce_checksum
@@ -843,11 +894,20 @@ def run_config(cfg_name, args, engine_factory, dist, rank, world, local, backend
         # y == x: the wall-clock interval holds the K restores of x as well; the step time of an in-place pass is the sum of the
         # K launches' own event-pair durations (timed_steps), which is what `value` and `ms_per_step` are built from here
         elapsed = kern_ms[0] * steps * 1e-3
-    per_launch = engine.probe_steps(min(steps, 50)) if hasattr(engine, "probe_steps") else list(kern_ms)  # outside the timed region
+    if dump_dir and rank == 0:
+        dump_outputs(engine, cfg, dump_dir)
+    per_launch = []
+    if full:
+        per_launch = engine.probe_steps(min(steps, 50)) if hasattr(engine, "probe_steps") else list(kern_ms)  # outside the timed region
     t = torch.tensor([elapsed], dtype=torch.float64, device=rdev)
     if dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed_max = float(t.item())
+    a = argparse.Namespace(**{**vars(args), "steps": steps, "warmup": warmup, "settle_ms": settle_ms,
+                              "lanes": lanes_override, "frames": frames_override})
+    if not full:  # a plain run: the headline of the timed region, nothing that takes launches of its own
+        line = report(cfg_name, cfg, a, world, lanes_rank, frames, elapsed_max, kern_ms, untimed, engine.kernel_name(), total_lanes, inplace)
+        return (line if rank == 0 else None), engine
     med_us = int(round(statistics.median(per_launch) * 1e3)) if per_launch else 0
     copy_gbs = engine.copy_rate() if (rank == 0 and hasattr(engine, "copy_rate")) else None
     sample = C5_CPU_LANES if cfg_name == "c5" and world == 1 and lanes_rank > C5_CPU_LANES else 0
@@ -856,8 +916,6 @@ def run_config(cfg_name, args, engine_factory, dist, rank, world, local, backend
     per_rank = gather_ints([sums[0], sums[1], med_us, lane_lo, lanes_rank], dist, rdev)
     if rank != 0:
         return None, engine
-    a = argparse.Namespace(**{**vars(args), "steps": steps, "warmup": warmup, "settle_ms": settle_ms,
-                              "lanes": lanes_override, "frames": frames_override})
     line = report(cfg_name, cfg, a, world, lanes_rank, frames, elapsed_max, kern_ms, untimed, engine.kernel_name(), total_lanes, inplace)
     if copy_gbs:
         line["roofline"]["copy_gbs"] = round(copy_gbs, 1)
@@ -919,18 +977,20 @@ def rank_main(args, engine_factory=HipEngine):
         rccl_ranks = int(one.item())
         assert rccl_ranks == dist.get_world_size() == world
 
+    full = bool(getattr(args, "full", False))
     line, engine = run_config(args.config, args, engine_factory, dist, rank, world, local, backend, args.steps, args.warmup,
-                              args.settle_ms, args.lanes, args.frames, inplace=bool(getattr(args, "inplace", False)))
+                              args.settle_ms, args.lanes, args.frames, inplace=bool(getattr(args, "inplace", False)), full=full,
+                              dump_dir=getattr(args, "dump_outputs", None))
     x_host = getattr(engine, "x_host", None)
     engine.free()
     sub = None
-    if args.config == "c2" and not args.no_c5 and (args.c5_lanes or not (args.lanes or args.frames)):
+    if full and args.config == "c2" and not args.no_c5 and (args.c5_lanes or not (args.lanes or args.frames)):
         # the strong-scaling job beside the weak-scaling headline: 2^20 / N lanes per rank
         sub, e5 = run_config("c5", args, engine_factory, dist, rank, world, local, backend, min(args.steps, 20),
                              args.warmup, min(args.settle_ms, 100.0), args.c5_lanes, args.c5_frames)
         e5.free()
     subs = {}
-    if args.config == "c2" and not (args.lanes or args.frames):
+    if full and args.config == "c2" and not (args.lanes or args.frames):
         # the other single-GPU configurations of BASELINE.json beside the headline: own timed region, roofline and integrity
         families = getattr(engine_factory, "FAMILIES", ("biquad",))
         for name, skip in (("c3", args.no_c3), ("c4", args.no_c4)):
@@ -940,7 +1000,7 @@ def rank_main(args, engine_factory=HipEngine):
                                        args.warmup, min(args.settle_ms, 100.0), 0, 0)
             e.free()
     lm_subs = {}
-    if args.config == "c2" and args.layout == "frame" and not getattr(args, "no_lane_major", False) and not (args.lanes or args.frames):
+    if full and args.config == "c2" and args.layout == "frame" and not getattr(args, "no_lane_major", False) and not (args.lanes or args.frames):
         # LaneMajor (`[lane][frame]`, the reference's native lane view, dsp-process/src/view.rs:176-196) of C2, C3 and C4: the same
         # tensors transposed, own timed region, roofline and integrity each
         families = getattr(engine_factory, "FAMILIES", ("biquad",))
@@ -952,7 +1012,7 @@ def rank_main(args, engine_factory=HipEngine):
                                           args.warmup, min(args.settle_ms, 100.0), 0, 0)
             e.free()
     ip_subs = {}
-    if (args.config == "c2" and args.layout == "frame" and not getattr(args, "no_inplace", False) and getattr(engine_factory, "INPLACE", False)
+    if (full and args.config == "c2" and args.layout == "frame" and not getattr(args, "no_inplace", False) and getattr(engine_factory, "INPLACE", False)
             and not (args.lanes or args.frames)):
         # the reference's own benchmarked mode: SplitInplace::inplace (dsp-process/src/process.rs:135-142; "slice inplace",
         # tests/embedded/README.md) — C2 and (unless --no-c5) C5 with y == x, same inputs, so the checksums on file hold
@@ -985,7 +1045,7 @@ def rank_main(args, engine_factory=HipEngine):
         if ip_subs:
             keep = ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "dtype", "config", "roofline", "integrity")
             line["inplace"] = {name: {k: sl[k] for k in keep} for name, sl in ip_subs.items()}
-        if world == 1 and not args.no_cpu and CONFIGS[args.config].get("family", "biquad") == "biquad":
+        if full and world == 1 and not args.no_cpu and CONFIGS[args.config].get("family", "biquad") == "biquad":
             cb = cpu_baseline(args.config, CONFIGS[args.config], x_host, args.layout)
             integ = line["integrity"]
             if cb["oracle_checksum_lanes"] == line["config"]["lanes_per_gpu"]:
@@ -997,7 +1057,7 @@ def rank_main(args, engine_factory=HipEngine):
             line["cpu_baseline"] = cb
         else:
             line["cpu_baseline"] = None
-        if world == 1 and args.config == "c2" and not getattr(args, "no_guard", False) and not (args.lanes or args.frames) and getattr(engine_factory, "GUARD", False):
+        if full and world == 1 and args.config == "c2" and not getattr(args, "no_guard", False) and not (args.lanes or args.frames) and getattr(engine_factory, "GUARD", False):
             # performance guard (tools/perf_guard.py): the shapes whose rate rides on the paced sweep schedule, against committed floors
             from tools import perf_guard
 
@@ -1034,14 +1094,19 @@ def parse_args(argv=None):
     ap.add_argument("--layout", choices=["frame", "lane"], default="frame")
     ap.add_argument("--lanes", type=int, default=0, help="override the configuration's lane count (diagnostics)")
     ap.add_argument("--frames", type=int, default=0, help="override the samples per lane (diagnostics)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-c5", action="store_true", help="skip the C5 strong-scaling sub-object of the default run")
-    ap.add_argument("--no-lane-major", action="store_true", help="skip the LaneMajor sub-objects (C2, C3, C4) of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the sub-objects of the other configurations, layouts and "
+                         "in-place runs, integrity, per-launch and copy probes, cpu_baseline, perf_guard")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write y and the state of the last timed step to DIR/*.npy (float32 / float64, a fixed lane sample above 48 MiB)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg of the --full run")
+    ap.add_argument("--no-c5", action="store_true", help="skip the C5 strong-scaling sub-object of the --full run")
+    ap.add_argument("--no-lane-major", action="store_true", help="skip the LaneMajor sub-objects (C2, C3, C4) of the --full run")
     ap.add_argument("--inplace", action="store_true", help="run the configuration itself in place (y == x; profiling runs of the in-place mode)")
-    ap.add_argument("--no-inplace", action="store_true", help="skip the in-place (y == x) sub-objects (C2, C5) of the default run")
-    ap.add_argument("--no-guard", action="store_true", help="skip the perf_guard object (tools/perf_guard.py) of the default run")
-    ap.add_argument("--no-c3", action="store_true", help="skip the C3 (HbfDec /16) sub-object of the default run")
-    ap.add_argument("--no-c4", action="store_true", help="skip the C4 (lock-in) sub-object of the default run")
+    ap.add_argument("--no-inplace", action="store_true", help="skip the in-place (y == x) sub-objects (C2, C5) of the --full run")
+    ap.add_argument("--no-guard", action="store_true", help="skip the perf_guard object (tools/perf_guard.py) of the --full run")
+    ap.add_argument("--no-c3", action="store_true", help="skip the C3 (HbfDec /16) sub-object of the --full run")
+    ap.add_argument("--no-c4", action="store_true", help="skip the C4 (lock-in) sub-object of the --full run")
     ap.add_argument("--c5-lanes", type=int, default=0, help="total lanes of the C5 sub-object (diagnostics; default 2^20)")
     ap.add_argument("--c5-frames", type=int, default=0, help="samples per lane of the C5 sub-object (diagnostics; default 4096)")
     return ap.parse_args(argv)

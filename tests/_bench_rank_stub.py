@@ -60,6 +60,13 @@ class OracleEngine:
             ts.append((time.perf_counter() - t0) * 1e3)
         return lambda: ts
 
+    def reset_state(self):
+        self.state[:] = 0
+
+    def outputs(self, lane_idx):
+        y = self.y if self.layout == self.H.FM else self.y.T  # [frame][lane]
+        return y[:, lane_idx], self.state[:, lane_idx]
+
     def verify(self, sample_lanes=0):
         self.state[:] = 0
         self.step()

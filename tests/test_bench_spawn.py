@@ -62,7 +62,7 @@ def test_two_ranks_started_by_bench_spawn_print_one_line(tmp_path):
 
     out = tmp_path / "line.txt"
     argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--settle-ms", "0", "--lanes", "192", "--frames", "40",
-            "--c5-lanes", "1000", "--c5-frames", "48"]
+            "--c5-lanes", "1000", "--c5-frames", "48", "--full"]
     env = dict(os.environ, IDSP_BENCH_LAUNCHER="self-spawned torch.distributed.run")
     env.pop("WORLD_SIZE", None)
     with open(out, "w") as fh:
@@ -161,7 +161,7 @@ def test_eight_ranks_rendezvous_and_c5_blocks(tmp_path):
 
     out = tmp_path / "line8.txt"
     argv = ["--gpus", "8", "--steps", "2", "--warmup", "1", "--settle-ms", "0", "--lanes", "64", "--frames", "24",
-            "--c5-lanes", "2056", "--c5-frames", "24"]
+            "--c5-lanes", "2056", "--c5-frames", "24", "--full"]
     env = dict(os.environ, IDSP_BENCH_LAUNCHER="self-spawned torch.distributed.run")
     env.pop("WORLD_SIZE", None)
     with open(out, "w") as fh:
@@ -176,3 +176,73 @@ def test_eight_ranks_rendezvous_and_c5_blocks(tmp_path):
     assert line["c5"]["ranks"]["first_lane"] == [lo for lo, _ in shards]
     assert line["c5"]["ranks"]["lanes"] == [hi - lo for lo, hi in shards] and sum(line["c5"]["ranks"]["lanes"]) == 2056
     assert list(line)[-1] == "summary" and set(line["summary"]) >= {"c2", "c5"}
+
+
+def _plain_run(out_dir, *extra):
+    """One rank of the stub with no launcher around it (a plain run): (the JSON line, {name: array} that --dump-outputs wrote)."""
+    argv = [sys.executable, STUB, "--steps", "3", "--settle-ms", "0", "--lanes", "192", "--frames", "40",
+            "--dump-outputs", str(out_dir), *extra]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run(argv, capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+    assert r.returncode == 0, r.stderr
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0]), {name: np.load(out_dir / f"{name}.npy") for name in ("y", "state", "lanes")}
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_the_last_timed_step(tmp_path):
+    """Without --full: exactly --steps timed steps, `ms_per_step`, and nothing that takes runs of its own.  --dump-outputs writes
+    y and the state the last timed step handed back — the oracle's after 3 passes from the stream's start, whatever the warm-up."""
+    import bench
+    from idsp_amd import _abi
+    from tests import _harness as H
+
+    line, got = _plain_run(tmp_path / "a", "--warmup", "1")
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["metric"] == bench.CONFIGS["c2"]["metric"]
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "i32"
+    assert abs(line["value"] - 192 * 40 / (line["ms_per_step"] * 1e-3) / 1e6) < 1e-2 * line["value"]
+    assert not {"c3", "c4", "c5", "lane_major", "inplace", "integrity", "perf_guard"} & set(line) and line["cpu_baseline"] is None
+    assert list(line)[-1] == "summary" and list(line["summary"]) == ["c2"]
+    o = H.oracle()
+    q = _abi.BiquadI32()
+    assert o.fn["biquad_i32_from_sos"]((C.c_double * 6)(*bench.lowpass_sos(bench.F0)), bench.FRAC, C.byref(q)) == 0
+    x = bench.c2_input_host(40, 192, "frame", 0)
+    st, y = np.zeros((4, 192), np.uint32), np.empty_like(x)
+    for _ in range(3):
+        assert o.stream("biquad_i32_df1", (_abi.BiquadI32 * 1)(q), 1, st, x, y, 192, 40, H.FM) == 0
+    assert got["y"].dtype == np.float64 and np.array_equal(got["y"], y.astype(np.float64))
+    assert got["state"].dtype == np.float64 and np.array_equal(got["state"], st.astype(np.float64))
+    assert np.array_equal(got["lanes"], np.arange(192))
+    _, again = _plain_run(tmp_path / "b", "--warmup", "4")
+    assert all(np.array_equal(got[k], again[k]) for k in got)
+
+
+def test_dump_outputs_samples_large_outputs_within_the_size_limit(tmp_path):
+    """Outputs larger than the limit are dumped as a fixed, sorted lane sample: the same lanes every time, y and state alike."""
+    import bench
+
+    class Big:  # values are a function of (frame, lane): nothing the size of the full output is allocated
+        lanes, frames = 1 << 20, 4096
+
+        def __init__(self, dtype, width):
+            self.dtype, self.width = dtype, width
+
+        def outputs(self, idx):
+            f = np.arange(self.frames)[:, None]
+            y = ((f * 7 + idx[None, :]) % 1000003).astype(self.dtype)
+            y = np.stack([y, -y], axis=-1) if self.width == 2 else y
+            return y, (np.arange(3)[:, None] * self.lanes + idx[None, :]).astype(np.uint32)
+
+    for name, dtype, width in (("c5", np.float32, 1), ("c4", np.int32, 2)):
+        cfg = dict(bench.CONFIGS[name], state_words=3)
+        dirs = [tmp_path / f"{name}_{i}" for i in range(2)]
+        for d in dirs:
+            bench.dump_outputs(Big(dtype, width), cfg, str(d))
+        assert sum(p.stat().st_size for p in dirs[0].iterdir()) <= 64 << 20
+        got = {k: np.load(dirs[0] / f"{k}.npy") for k in ("y", "state", "lanes")}
+        lanes = got["lanes"].astype(np.int64)
+        assert 500 < len(lanes) < Big.lanes and np.all(np.diff(lanes) > 0) and lanes[-1] < Big.lanes
+        assert got["y"].dtype == (np.float32 if dtype == np.float32 else np.float64)
+        assert got["y"].shape == ((Big.frames, len(lanes), 2) if width == 2 else (Big.frames, len(lanes)))
+        assert np.array_equal(got["state"][2], 2 * Big.lanes + lanes)
+        assert all(np.array_equal(got[k], np.load(dirs[1] / f"{k}.npy")) for k in got)
