@@ -28,7 +28,7 @@ int fail(int code, const char *fmt, ...)
 
 namespace {
 struct LastKernel {
-    const char *kernel = nullptr, *detail = nullptr, *also = nullptr;
+    const char *kernel = nullptr, *detail = nullptr, *also[2] = {nullptr, nullptr};
     char text[768] = {0};
 };
 LastKernel &last_kernel()
@@ -44,9 +44,14 @@ void note_kernel(const char *kernel, const char *detail)
     LastKernel &k = last_kernel();
     k.kernel = kernel;
     k.detail = detail;
-    k.also = nullptr;
+    k.also[0] = k.also[1] = nullptr;
 }
-void note_kernel_also(const char *also) { last_kernel().also = also; }
+// appended after what an earlier note_kernel_also() of the same launch recorded (the sweep's frames per segment, then a second stream's kernel)
+void note_kernel_also(const char *also)
+{
+    LastKernel &k = last_kernel();
+    k.also[k.also[0] ? 1 : 0] = also;
+}
 const char *noted_kernel() { return last_kernel().kernel; }
 
 namespace {
@@ -129,10 +134,10 @@ const char *idsp_last_kernel(void)
         // `detail` is typeid(Processor).name(): demangle it for the reader
         int status = 0;
         char *dm = abi::__cxa_demangle(k.detail, nullptr, nullptr, &status);
-        snprintf(k.text, sizeof(k.text), "%s<%s>%s", k.kernel, status == 0 && dm ? dm : k.detail, k.also ? k.also : "");
+        snprintf(k.text, sizeof(k.text), "%s<%s>%s%s", k.kernel, status == 0 && dm ? dm : k.detail, k.also[0] ? k.also[0] : "", k.also[1] ? k.also[1] : "");
         free(dm);
     } else {
-        snprintf(k.text, sizeof(k.text), "%s%s", k.kernel, k.also ? k.also : "");
+        snprintf(k.text, sizeof(k.text), "%s%s%s", k.kernel, k.also[0] ? k.also[0] : "", k.also[1] ? k.also[1] : "");
     }
     return k.text;
 }

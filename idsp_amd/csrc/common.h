@@ -108,7 +108,8 @@ inline SideStream *side_stream(hipStream_t caller)
 
 // Name of the kernel the most recent launch on this thread dispatched to (idsp_last_kernel()).
 void note_kernel(const char *kernel, const char *detail = nullptr);
-// a second kernel the same call ran beside it (appended to the text; cleared by the next note_kernel())
+// a suffix: a detail of the launch or a second kernel the same call ran beside it (appended to the text, at most two per launch;
+// cleared by the next note_kernel())
 void note_kernel_also(const char *also);
 // the name the most recent note_kernel() on this thread recorded (a static string; NULL before the first launch)
 const char *noted_kernel();

@@ -591,7 +591,8 @@ int launch_sweep(const typename P::Params &prm, uint32_t *st, const typename P::
     // few lanes per workgroup (below 32768 + lanes in all): several frames per one-KiB segment, so that a tile stays 8 KiB of real samples
     // (IDSP_DIAG=1 IDSP_SWEEP_NO_FPS=1: one frame per segment)
     static const bool no_fps = diag_env("IDSP_SWEEP_NO_FPS") != nullptr;
-    if (g.lpt == 1 && sizeof(typename P::Out) == 4 && g.bw <= 128 && !no_fps) {
+    const bool fps_form = g.lpt == 1 && sizeof(typename P::Out) == 4 && g.bw <= 128 && !no_fps;
+    if (fps_form) {
         unsigned f = 256u / g.bw;
         while (f > 1 && (size_t(f - 1) * kSweepT * (xl > yl ? xl : yl) + 256) * 4 >= (size_t(1) << 32)) f--;  // per-thread byte offsets are 32-bit
         g.fps = f;
@@ -605,6 +606,12 @@ int launch_sweep(const typename P::Params &prm, uint32_t *st, const typename P::
                                           "stream_frame_major_sweep[4 blocks/workgroup, XCD-contiguous]", "stream_frame_major_sweep[8 blocks/workgroup, XCD-contiguous]",
                                           "stream_frame_major_sweep[16 blocks/workgroup, XCD-contiguous]"};
     note_kernel(xcdc && g.grid >= 8 ? names_x[k] : names[k], typeid(P).name());
+    if (fps_form) {
+        // the frames per segment, 1 where the 32-bit guard above brought them down (tests pin both sides of it)
+        static thread_local char fps_text[32];
+        snprintf(fps_text, sizeof(fps_text), " [%u frame%s/segment]", g.fps, g.fps == 1 ? "" : "s");
+        note_kernel_also(fps_text);
+    }
     if constexpr (kMax >= 16) {
         if (g.lpt == 16) return launch_sweep_lpt<P, 16>(prm, st, x, y, lanes, frames, xl, yl, sp, g, s, xcdc && g.grid >= 8);
     }
