@@ -91,6 +91,8 @@ class FmDisc(C.Structure):
 
 
 FM_DISC_STATE_WORDS = 7
+PLL_STATE_WORDS = 9
+PLL_PHASE, PLL_FREQUENCY, PLL_BOTH = 0, 1, 2
 
 
 class Cic(C.Structure):
@@ -292,6 +294,20 @@ UTILS = {
     "multi_biquad_i32_df1": (_I, [_P, _P, _SZ, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _SZ, _SZ, _I]),
     "multi_biquad_f32_df2t": (_I, [_P, _P, _SZ, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _SZ, _SZ, _I]),
 }
+
+# phase consumers (product only: the checker library has no twin, parity rests on tests/_phase_spec.py); every
+# prototype as (restype, argtypes), merged into UTILS so that exported_names() and bind(..., utils=True) cover them
+_PHASE_SIG = [_P, _P, _P, _SZ, _SZ, _I, _P]  # state, x, y, lanes, frames, layout, stream
+PHASE = {
+    "clamp_wrap_i32": (_I, _PHASE_SIG),
+    "unwrap_i32": (_I, _PHASE_SIG),
+    "unwrap_i32_phase": (_I, _PHASE_SIG),
+    "pll_state_words": (_SZ, []),
+    "pll_i32": (_I, [_P, _P, _P, _P, _SZ, _SZ, _I, _I, _P]),  # ba, state, x, y, lanes, frames, layout, output, stream
+    "pll_from_zpk": (_I, [_D, _D, _D, _P]),
+    "pll_from_bandwidth": (_I, [_D, _D, _P]),
+}
+UTILS.update(PHASE)
 
 SHARD_FN = C.CFUNCTYPE(_I, _P, _I, _SZ, _SZ, _P)  # idsp_shard_fn
 

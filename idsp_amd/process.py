@@ -21,6 +21,9 @@ own:
     Lockin<[Lowpass<N>; K]>, Accu        (lockin.rs, accu.rs) Lockin([...]).lanes(N, step=...)
     Lockin<C> biquad arms / external LO  (lockin.rs:16-27)    Lockin([Biquad...]), LockinLo(arms, N).process(x, lo, y)
     Split::stateful(Cic::new(rate)).decimate() (cic.rs:338) Cic(N, rate).decimate().lanes(n)
+    PLL / PLLState                       (pll.rs:33-107)  PLL.from_bandwidth(bw, split).lanes(N, output=...)
+    Unwrapper<i64> / ClampWrap<W<i32>>   (unwrap.rs:109-194) Unwrapper().lanes(N), ClampWrap().lanes(N)
+    overflowing_sub / saturating_scale   (unwrap.rs:73-101) overflowing_sub(y, x), saturating_scale(lo, hi, shift)
     cossin(phase)                        (cossin.rs:14)  cossin(phases)
     atan2(y, x) / Complex::arg           (atan2.rs:66)   atan2(xy)
 
@@ -44,7 +47,7 @@ __all__ = [
     "FrameMajor", "LaneMajor", "View", "ViewMut", "Biquad", "BiquadClamp", "Cascade",
     "DirectForm1", "DirectForm2Transposed", "DirectForm1Wide", "DirectForm1Dither", "DirectForm",
     "Split", "Lanes", "ByLane", "HbfDecCascade", "HbfIntCascade", "FirSym", "Cic", "Normal", "Wdf", "HBF_TAPS", "HBF_TAPS_98",
-    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "FmDisc", "cossin", "atan2", "sos", "sos_clamp_wide", "IdspError",
+    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "FmDisc", "PLL", "Unwrapper", "ClampWrap", "overflowing_sub", "saturating_scale", "cossin", "atan2", "sos", "sos_clamp_wide", "IdspError",
 ]
 
 FrameMajor = _abi.FRAME_MAJOR  # dsp-process/src/view.rs:10
@@ -879,6 +882,141 @@ class FmDisc(_LaneOp):
     def _run(self, x, y, frames, layout):
         call("fm_disc_i32", C.byref(self.cfg), C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()),
              C.c_void_p(y.data_ptr()), self.n_lanes, frames, layout, _stream_ptr(x))
+
+
+# --------------------------------------------------------------------------
+# phase consumers: PLL, Unwrapper, ClampWrap
+# --------------------------------------------------------------------------
+def _i32(v: int) -> int:
+    return ((int(v) + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
+
+
+def overflowing_sub(y: int, x: int):
+    """`overflowing_sub(y, x) -> (delta, wrap)` for i32 (src/unwrap.rs:73-80): the wrapped difference `y - x` and the signum of
+    the overflow as -1 (`Wrap::Negative`), 0 (`Wrap::None`) or 1 (`Wrap::Positive`).  Host arithmetic."""
+    y, x = _i32(y), _i32(x)
+    delta = _i32(y - x)
+    return delta, int(delta >= 0) - int(y >= x)
+
+
+def saturating_scale(lo: int, hi: int, shift: int) -> int:
+    """`saturating_scale(lo, hi, shift)` (src/unwrap.rs:90-101): `hi:lo` scaled down by `shift` bits into one i32, saturating
+    monotonically.  1 <= shift <= 32 (the reference's debug_assert!s).  Host arithmetic."""
+    if not 1 <= shift <= 32:
+        raise ValueError("shift must be in 1..=32")
+    lo, hi = _i32(lo), _i32(hi)
+    hi_range = -(1 << (shift - 1))
+    if hi <= hi_range:
+        return _i32(-(1 << 31) - hi_range)
+    if -hi <= hi_range:
+        return _i32(hi_range + (1 << 31))
+    return _i32((lo >> shift) + _i32(hi << (32 - shift)))
+
+
+def _i64_of(lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
+    """two int32 state planes (lo, hi) -> int64"""
+    return (hi.to(torch.int64) << 32) | (lo.to(torch.int64) & 0xFFFFFFFF)
+
+
+class PLL:
+    """`PLL { ba: [Q32<32>; 3] }` (src/pll.rs:33-58): `ba` as `Q32<32>` bits.  `.lanes(n)` gives the `Split<Lanes<PLL>, [PLLState; n]>`."""
+
+    def __init__(self, ba: Sequence[int]):
+        if len(ba) != 3:
+            raise ValueError("ba: [Q32<32>; 3]")
+        self.ba = [_i32(v) for v in ba]
+
+    @classmethod
+    def from_zpk(cls, zero: float, pole: float, gain: float) -> "PLL":
+        """`PLL::from_zpk` (src/pll.rs:42-46), f32 arithmetic in the library."""
+        ba = (C.c_int32 * 3)()
+        call("pll_from_zpk", float(zero), float(pole), float(gain), ba)
+        return cls(list(ba))
+
+    @classmethod
+    def from_bandwidth(cls, bw: float, split: float = 4.0) -> "PLL":
+        """`PLL::from_bandwidth` (src/pll.rs:51-57)."""
+        ba = (C.c_int32 * 3)()
+        call("pll_from_bandwidth", float(bw), float(split), ba)
+        return cls(list(ba))
+
+    def lanes(self, n: int, output: str = "phase", device="cuda") -> "PLLLanes":
+        return PLLLanes(self, n, output, device)
+
+
+class PLLLanes(_LaneOp):
+    """`PLL::process` per lane (src/pll.rs:90-107).  `output`: "phase" (what `process` returns), "frequency"
+    (`state.frequency()` after each sample) or "both" (y[..., 2] = {phase, frequency})."""
+
+    _OUTPUTS = {"phase": (_abi.PLL_PHASE, 1), "frequency": (_abi.PLL_FREQUENCY, 1), "both": (_abi.PLL_BOTH, 2)}
+
+    def __init__(self, pll: PLL, n_lanes: int, output: str = "phase", device="cuda"):
+        if output not in self._OUTPUTS:
+            raise ValueError(f"output must be one of {sorted(self._OUTPUTS)}")
+        self._output, self.out_width = self._OUTPUTS[output]
+        self.ba = (C.c_int32 * 3)(*pll.ba)
+        super().__init__(n_lanes, _abi.PLL_STATE_WORDS, device)
+
+    def _run(self, x, y, frames, layout):
+        call("pll_i32", self.ba, C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
+             self.n_lanes, frames, layout, self._output, _stream_ptr(x))
+
+    def phase(self) -> torch.Tensor:
+        """`PLLState::phase()` of every lane (src/pll.rs:79-81), int32."""
+        return self.state[8].clone()
+
+    def frequency(self) -> torch.Tensor:
+        """`PLLState::frequency()` of every lane (src/pll.rs:84-86), int32."""
+        return self.state[7].clone()
+
+
+class Unwrapper:
+    """`Unwrapper<i64>` fed i32 (src/unwrap.rs:109-156).  `output`: "dx" (what `process` returns, i32) or "phase" (the
+    running `phase::<i64>()`, i64)."""
+
+    def lanes(self, n: int, output: str = "dx", device="cuda") -> "UnwrapperLanes":
+        return UnwrapperLanes(n, output, device)
+
+
+class UnwrapperLanes(_LaneOp):
+    _OUTPUTS = {"dx": ("unwrap_i32", torch.int32), "phase": ("unwrap_i32_phase", torch.int64)}
+
+    def __init__(self, n_lanes: int, output: str = "dx", device="cuda"):
+        if output not in self._OUTPUTS:
+            raise ValueError(f"output must be one of {sorted(self._OUTPUTS)}")
+        self._entry, self.dtype_out = self._OUTPUTS[output]
+        super().__init__(n_lanes, 2, device)
+
+    def _run(self, x, y, frames, layout):
+        call(self._entry, C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
+             self.n_lanes, frames, layout, _stream_ptr(x))
+
+    def phase(self) -> torch.Tensor:
+        """`Unwrapper::phase::<i64>()` of every lane (src/unwrap.rs:130-136)."""
+        return _i64_of(self.state[0], self.state[1])
+
+    def wraps(self, shift: int) -> torch.Tensor:
+        """`Unwrapper::wraps::<i32, S>()` of every lane (src/unwrap.rs:119-127), int32."""
+        if not 1 <= shift <= 63:
+            raise ValueError("shift must be in 1..=63")
+        y = self.phase()
+        return ((y >> shift).to(torch.int32) + ((y >> (shift - 1)).to(torch.int32) & 1)).to(torch.int32)
+
+
+class ClampWrap:
+    """`ClampWrap<W<i32>>` (src/unwrap.rs:166-194): wraps of the input become saturation until the matching un-wrap."""
+
+    def lanes(self, n: int, device="cuda") -> "ClampWrapLanes":
+        return ClampWrapLanes(n, device)
+
+
+class ClampWrapLanes(_LaneOp):
+    def __init__(self, n_lanes: int, device="cuda"):
+        super().__init__(n_lanes, 2, device)
+
+    def _run(self, x, y, frames, layout):
+        call("clamp_wrap_i32", C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
+             self.n_lanes, frames, layout, _stream_ptr(x))
 
 
 def cossin(p: torch.Tensor) -> torch.Tensor:

@@ -787,6 +787,40 @@ typedef struct idsp_fm_disc {
 int idsp_fm_disc_i32(const idsp_fm_disc *cfg, void *state, const int32_t *x, int32_t *y,
                      size_t lanes, size_t frames, int layout, void *stream);
 
+/* ---- phase consumers: what follows `arg()`, the discriminator or a DDS phase in a demodulation chain.  Wrapping i32 phase
+ * in (2^32 = one turn), one independent recurrence per lane, all integer and bit-exact; x and y in either layout, y == x
+ * allowed where the output element is 4 bytes.  The all-zero state is the reference's `Default::default()`.
+ *
+ * `ClampWrap<W<i32>>` (src/unwrap.rs:166-194, `overflowing_sub` :73-80): maps wraps of the input to saturation.
+ * State words per lane: { x0, clamp as -1 / 0 / 1 (`Wrap`, src/unwrap.rs:18-27) }. */
+int idsp_clamp_wrap_i32(void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout, void *stream);
+
+/* `Unwrapper<i64>` fed i32 (src/unwrap.rs:109-156).  State words per lane: { y lo, y hi }.
+ *   idsp_unwrap_i32:       dx[index(f,l)] = `process(x)`, the wrapped difference to the previous sample (i32)
+ *   idsp_unwrap_i32_phase: y[index(f,l)]  = `phase::<i64>()` after the sample, the unwrapped running phase (i64)
+ * The two may be mixed on one state; `wraps::<i32, S>()` (:119-127) is host arithmetic on the state. */
+int idsp_unwrap_i32(void *state, const int32_t *x, int32_t *dx, size_t lanes, size_t frames, int layout, void *stream);
+int idsp_unwrap_i32_phase(void *state, const int32_t *x, int64_t *y, size_t lanes, size_t frames, int layout, void *stream);
+
+/* `PLL` (src/pll.rs:33-107): type-2, order-3 phase-locked loop on a sampled phase.  ba = `PLL::ba` as `Q32<32>` bits.
+ * State words per lane (`PLLState`, :62-75): { clamp.x0, clamp.clamp as -1 / 0 / 1, z0, y0, f0 lo, f0 hi, f lo, f hi, y }.
+ * output: IDSP_PLL_PHASE      y[index(f,l)] = `process(x)`, the output phase (:106)
+ *         IDSP_PLL_FREQUENCY  y[index(f,l)] = `state.frequency()` after the sample (:84-86)
+ *         IDSP_PLL_BOTH       y[index(f,l)*2 + {0: phase, 1: frequency}] (y holds 2*lanes*frames words; no in-place form)
+ * `state.phase()` / `state.frequency()` after a call are state word 8 / state word 7. */
+#define IDSP_PLL_STATE_WORDS 9
+#define IDSP_PLL_PHASE 0
+#define IDSP_PLL_FREQUENCY 1
+#define IDSP_PLL_BOTH 2
+size_t idsp_pll_state_words(void);
+int idsp_pll_i32(const int32_t ba[3], void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout,
+                 int output, void *stream);
+/* `PLL::from_zpk(zero, pole, gain)` (src/pll.rs:42-46) and `PLL::from_bandwidth(bw, split)` (:51-57): host code, no GPU needed.
+ * The arguments are narrowed to f32 first and the arithmetic runs in f32 in the reference's order; each coefficient is
+ * `Q32::<32>::from_f32`: times 2^32, rounded half away from zero, saturating (NaN -> 0). */
+int idsp_pll_from_zpk(double zero, double pole, double gain, int32_t ba[3]);
+int idsp_pll_from_bandwidth(double bw, double split, int32_t ba[3]);
+
 /* ------------------------------------------------------------------------ */
 /* lane split over several devices in ONE process: idsp_multi_*             */
 /* ------------------------------------------------------------------------ */

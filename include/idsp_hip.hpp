@@ -21,6 +21,9 @@
 //   Split::stateful(Cic::new(rate)).decimate()/.interpolate() (cic.rs:338-346)  CicDecimator<T> / CicInterpolator<T>
 //   cossin(phase)                       (cossin.rs:14)          cossin(phases, out)
 //   atan2(y, x) / Complex::arg          (atan2.rs:66)           atan2(xy, out)
+//   PLL / PLLState                      (pll.rs:33-107)         PLL::from_bandwidth(bw, split).lanes(n)
+//   Unwrapper<i64> / ClampWrap<W<i32>>  (unwrap.rs:109-194)     Unwrapper(n) / ClampWrap(n)
+//   overflowing_sub / saturating_scale  (unwrap.rs:73-101)      overflowing_sub(y, x) / saturating_scale(lo, hi, shift)
 //
 // Misuse that is a `debug_assert!`/panic in the reference throws idsp_hip::Error.
 #pragma once
@@ -910,6 +913,160 @@ public:
 
 private:
     idsp_lockin_i32 cfg_{};
+    size_t lanes_;
+    void *stream_;
+    DeviceBuffer<uint32_t> state_;
+};
+
+// ------------------------------------------------------- phase consumers
+/// `Wrap` (src/unwrap.rs:15-27)
+enum class Wrap : int8_t { Negative = -1, None = 0, Positive = 1 };
+
+/// `overflowing_sub(y, x)` on i32 (src/unwrap.rs:73-80): the wrapped difference and the signum of the overflow.  Host arithmetic.
+inline std::pair<int32_t, Wrap> overflowing_sub(int32_t y, int32_t x)
+{
+    const int32_t delta = int32_t(uint32_t(y) - uint32_t(x));
+    return {delta, Wrap(int(delta >= 0) - int(y >= x))};
+}
+
+/// `saturating_scale(lo, hi, shift)` (src/unwrap.rs:90-101), 1 <= shift <= 32.  Host arithmetic.
+inline int32_t saturating_scale(int32_t lo, int32_t hi, uint32_t shift)
+{
+    require(shift >= 1 && shift <= 32, "shift must be in 1..=32");
+    const int64_t hi_range = -(int64_t(1) << (shift - 1)), min = std::numeric_limits<int32_t>::min();
+    if (hi <= hi_range) return int32_t(min - hi_range);
+    if (-int64_t(hi) <= hi_range) return int32_t(hi_range - min);
+    return int32_t(uint32_t(int64_t(lo) >> shift) + uint32_t(uint64_t(int64_t(hi)) << (32 - shift)));
+}
+
+class PLLLanes;
+/// `PLL { ba: [Q32<32>; 3] }` (src/pll.rs:33-58); the builders run in f32 inside the library, in the reference's order.
+struct PLL {
+    std::array<int32_t, 3> ba{};
+    static PLL from_zpk(float zero, float pole, float gain)
+    {
+        PLL p;
+        check(idsp_pll_from_zpk(zero, pole, gain, p.ba.data()));
+        return p;
+    }
+    static PLL from_bandwidth(float bw, float split)
+    {
+        PLL p;
+        check(idsp_pll_from_bandwidth(bw, split, p.ba.data()));
+        return p;
+    }
+    inline PLLLanes lanes(size_t n, void *stream = nullptr) const;
+};
+
+/// `Split<Lanes<PLL>, [PLLState; n]>` (src/pll.rs:60-107): zero state = `PLLState::default()`.
+class PLLLanes {
+public:
+    PLLLanes(const PLL &pll, size_t lanes, void *stream = nullptr)
+        : pll_(pll), lanes_(lanes), stream_(stream), state_(idsp_pll_state_words() * lanes)
+    {
+    }
+    DeviceBuffer<uint32_t> &state() { return state_; }
+    /// y = `process(x)`, the output phase (src/pll.rs:106); y may be x
+    template <class Layout>
+    void process_view(View<int32_t, Layout> x, ViewMut<int32_t, Layout> y)
+    {
+        run(x, y, IDSP_PLL_PHASE);
+    }
+    /// y = `state.frequency()` after each sample (src/pll.rs:84-86); y may be x
+    template <class Layout>
+    void process_view_frequency(View<int32_t, Layout> x, ViewMut<int32_t, Layout> y)
+    {
+        run(x, y, IDSP_PLL_FREQUENCY);
+    }
+    /// y = `{phase, frequency}` pairs: build the view with width 2
+    template <class Layout>
+    void process_view_both(View<int32_t, Layout> x, ViewMut<int32_t, Layout> y)
+    {
+        run(x, y, IDSP_PLL_BOTH);
+    }
+    /// `PLLState::phase()` / `PLLState::frequency()` of every lane (src/pll.rs:79-86)
+    std::vector<int32_t> phase() const { return word(8); }
+    std::vector<int32_t> frequency() const { return word(7); }
+
+private:
+    template <class Layout>
+    void run(View<int32_t, Layout> x, ViewMut<int32_t, Layout> y, int output)
+    {
+        require(x.frames == y.frames && x.lanes == lanes_ && y.lanes == lanes_, "view shape mismatch");
+        check(idsp_pll_i32(pll_.ba.data(), state_.data(), x.flat, y.flat, lanes_, x.frames, Layout::value, output, stream_));
+    }
+    std::vector<int32_t> word(size_t w) const
+    {
+        check(idsp_stream_sync(stream_));
+        const std::vector<uint32_t> st = state_.to_host();
+        std::vector<int32_t> out(lanes_);
+        for (size_t l = 0; l < lanes_; l++) out[l] = int32_t(st[w * lanes_ + l]);
+        return out;
+    }
+    PLL pll_;
+    size_t lanes_;
+    void *stream_;
+    DeviceBuffer<uint32_t> state_;
+};
+inline PLLLanes PLL::lanes(size_t n, void *stream) const { return PLLLanes(*this, n, stream); }
+
+/// `Unwrapper<i64>` fed i32, one per lane (src/unwrap.rs:109-156).
+class Unwrapper {
+public:
+    explicit Unwrapper(size_t lanes, void *stream = nullptr) : lanes_(lanes), stream_(stream), state_(2 * lanes) {}
+    DeviceBuffer<uint32_t> &state() { return state_; }
+    /// dx = `process(x)`, the wrapped difference to the previous sample; dx may be x
+    template <class Layout>
+    void process_view(View<int32_t, Layout> x, ViewMut<int32_t, Layout> dx)
+    {
+        require(x.frames == dx.frames && x.lanes == lanes_ && dx.lanes == lanes_, "view shape mismatch");
+        check(idsp_unwrap_i32(state_.data(), x.flat, dx.flat, lanes_, x.frames, Layout::value, stream_));
+    }
+    /// y = `phase::<i64>()` after each sample
+    template <class Layout>
+    void process_view_phase(View<int32_t, Layout> x, ViewMut<int64_t, Layout> y)
+    {
+        require(x.frames == y.frames && x.lanes == lanes_ && y.lanes == lanes_, "view shape mismatch");
+        check(idsp_unwrap_i32_phase(state_.data(), x.flat, y.flat, lanes_, x.frames, Layout::value, stream_));
+    }
+    /// `phase::<i64>()` of every lane (src/unwrap.rs:130-136)
+    std::vector<int64_t> phase() const
+    {
+        check(idsp_stream_sync(stream_));
+        const std::vector<uint32_t> st = state_.to_host();
+        std::vector<int64_t> y(lanes_);
+        for (size_t l = 0; l < lanes_; l++) y[l] = int64_t(uint64_t(st[l]) | (uint64_t(st[lanes_ + l]) << 32));
+        return y;
+    }
+    /// `wraps::<i32, S>()` of every lane (src/unwrap.rs:119-127), 1 <= shift <= 63
+    std::vector<int32_t> wraps(uint32_t shift) const
+    {
+        require(shift >= 1 && shift <= 63, "shift must be in 1..=63");
+        const std::vector<int64_t> y = phase();
+        std::vector<int32_t> w(lanes_);
+        for (size_t l = 0; l < lanes_; l++) w[l] = int32_t(uint32_t(y[l] >> shift) + (uint32_t(y[l] >> (shift - 1)) & 1u));
+        return w;
+    }
+
+private:
+    size_t lanes_;
+    void *stream_;
+    DeviceBuffer<uint32_t> state_;
+};
+
+/// `ClampWrap<W<i32>>`, one per lane (src/unwrap.rs:166-194).
+class ClampWrap {
+public:
+    explicit ClampWrap(size_t lanes, void *stream = nullptr) : lanes_(lanes), stream_(stream), state_(2 * lanes) {}
+    DeviceBuffer<uint32_t> &state() { return state_; }
+    template <class Layout>
+    void process_view(View<int32_t, Layout> x, ViewMut<int32_t, Layout> y)  // y may be x
+    {
+        require(x.frames == y.frames && x.lanes == lanes_ && y.lanes == lanes_, "view shape mismatch");
+        check(idsp_clamp_wrap_i32(state_.data(), x.flat, y.flat, lanes_, x.frames, Layout::value, stream_));
+    }
+
+private:
     size_t lanes_;
     void *stream_;
     DeviceBuffer<uint32_t> state_;

@@ -345,6 +345,62 @@ def lockin_generic(form, n, lanes, frames, layout, iters, tag):
            (12 if form == "phase" else 20) * lanes * frames, med, mn)
 
 
+def lowpass(order, cascade, lanes, frames, layout, iters, tag):
+    """`[Lowpass<N>; K]` alone (idsp_lowpass_i32): the nearest i64 recurrence to the PLL, 8 bytes per sample"""
+    cfg = _abi.LockinI32()
+    cfg.order, cfg.cascade = order, cascade
+    k = math.pi * (1 << 31) * 1e-3
+    for c in range(cascade):
+        if order == 1:
+            cfg.k[c][0] = int(k)
+        else:
+            cfg.k[c][0], cfg.k[c][1] = int(k * k / (1 << 32)), -int(k * math.sqrt(2.0))
+    x = torch.randint(-(1 << 28), 1 << 28, (lanes * frames,), dtype=torch.int32, device=dev)
+    x, y = out_like(x)
+    st = torch.zeros((2 * order * cascade, lanes), dtype=torch.int32, device=dev)
+
+    def run():
+        call("lowpass_i32", C.byref(cfg), p(st), p(x), p(y), lanes, frames, layout, sptr())
+
+    med, mn = timeit(run, iters)
+    report(f"{tag}:lowpass Lowpass<{order}>x{cascade} {'LM' if layout else 'FM'} {lanes}x{frames}", lanes * frames, "sample", 8 * lanes * frames, med, mn,
+           dispatch=call("last_kernel").decode())
+
+
+def phase(op, lanes, frames, layout, iters, tag):
+    """The phase consumers: op = "pll_phase" / "pll_frequency" / "pll_both" (idsp_pll_i32), "unwrap" (idsp_unwrap_i32), "unwrap_phase"
+    (idsp_unwrap_i32_phase, i64 out) or "clamp_wrap".  Input: per-lane phase ramps with noise, as a lock-in's `arg` output looks."""
+    step = torch.randint(-(1 << 27), 1 << 27, (lanes,), dtype=torch.int64, device=dev)
+    n = torch.arange(1, frames + 1, dtype=torch.int64, device=dev)
+    ramp = n[:, None] * step[None, :] if layout == 0 else step[:, None] * n[None, :]
+    ramp = ramp + torch.randint(-(1 << 20), 1 << 20, ramp.shape, dtype=torch.int64, device=dev)
+    x = (((ramp + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)).to(torch.int32).reshape(-1).contiguous()
+    del ramp
+    out_words = {"pll_both": 2, "unwrap_phase": 2}.get(op, 1)
+    if out_words == 1:
+        x, y = out_like(x)
+    else:
+        y = torch.empty(lanes * frames * 2, dtype=torch.int32, device=dev)
+    words = call("pll_state_words") if op.startswith("pll") else 2
+    st = torch.zeros((words, lanes), dtype=torch.int32, device=dev)
+    ba = (C.c_int32 * 3)()
+    call("pll_from_bandwidth", 1e-2, 4.0, ba)
+    if op.startswith("pll"):
+        output = {"pll_phase": _abi.PLL_PHASE, "pll_frequency": _abi.PLL_FREQUENCY, "pll_both": _abi.PLL_BOTH}[op]
+
+        def run():
+            call("pll_i32", ba, p(st), p(x), p(y), lanes, frames, layout, output, sptr())
+    else:
+        entry = {"unwrap": "unwrap_i32", "unwrap_phase": "unwrap_i32_phase", "clamp_wrap": "clamp_wrap_i32"}[op]
+
+        def run():
+            call(entry, p(st), p(x), p(y), lanes, frames, layout, sptr())
+
+    med, mn = timeit(run, iters)
+    report(f"{tag}:{op} {'LM' if layout else 'FM'} {lanes}x{frames}", lanes * frames, "sample", 4 * (1 + out_words) * lanes * frames, med, mn,
+           dispatch=call("last_kernel").decode())
+
+
 def copy_ref(nbytes, iters):
     a = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     b = torch.empty_like(a)
@@ -498,6 +554,16 @@ def main():
         biquad("cascade_i32_df1", torch.int32, 4, 65536, 4096, FM, 8, it, "f")
         biquad("biquad_i32_wide", torch.int32, 6, 65536, 4096, FM, 4, it, "f")
         hbf("int", 4, 16384, 4096, FM, max(3, it // 3), "f")
+    if want("phase"):  # PLL / Unwrapper / ClampWrap at the C2 shape, beside the nearest existing i64 recurrence
+        for layout in (FM, LM):
+            lowpass(2, 1, 65536, 4096, layout, it, "ph")
+            for op in ("pll_phase", "pll_both", "unwrap", "clamp_wrap"):
+                phase(op, 65536, 4096, layout, it, "ph")
+        if sel and "phase" in sel:
+            for layout in (FM, LM):
+                phase("pll_frequency", 65536, 4096, layout, it, "ph")
+                phase("unwrap_phase", 65536, 4096, layout, it, "ph")
+            lowpass(2, 2, 65536, 4096, FM, it, "ph")
     if want("lockinc"):  # `Lockin<C>` with biquad arms at the C4 shape (thread-per-lane stream kernels)
         for layout in (FM, LM):
             lockin_generic("phase", 1, 32768, 4096, layout, it, "C4g")
