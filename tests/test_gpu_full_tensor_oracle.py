@@ -22,6 +22,7 @@ import torch
 
 from idsp_amd import _abi
 from tests import _harness as H
+from tests._float_special import assert_same_float
 
 pytestmark = pytest.mark.gpu
 FM, LM = H.FM, H.LM
@@ -70,6 +71,7 @@ def test_c3_every_output_against_the_oracle(gpu):
     oracle_all_lanes(lambda s, a, b, n: o.cfgcall("hbf_dec_f32", cfg, s, a, b, n, frames, LM), x, want, st)
     got = yd.cpu().numpy()
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), int(H.ulp_diff_f32(got, want).max())
+    assert_same_float(want, got, "hbf_dec_f32 /16 LaneMajor, every output")
     assert np.array_equal(sd.cpu().numpy().view(np.uint32), st)
     assert gpu.fn["last_kernel"]().decode().startswith("hbf_dec_blk[LaneMajor]")
     # the same tensor FRAME_MAJOR ([frame][lane][R] chunks): every output again

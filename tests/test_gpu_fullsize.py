@@ -12,6 +12,7 @@ import torch
 
 from idsp_amd import _abi
 from tests import _harness as H
+from tests._float_special import assert_same_float
 
 pytestmark = pytest.mark.gpu
 FM, LM = H.FM, H.LM
@@ -85,6 +86,7 @@ def test_c3_hbf_dec16_16384_lanes(eng):
     ss = np.zeros((118, idx.size), np.uint32)
     assert o.cfgcall("hbf_dec_f32", cfg, ss, xs, ys, idx.size, frames, LM) == 0
     assert H.ulp_diff_f32(y.cpu().numpy()[idx], ys).max() == 0
+    assert_same_float(ys, y.cpu().numpy()[idx], "hbf_dec_f32 /16, sampled lanes")
     assert np.array_equal(st.cpu().numpy().view(np.uint32)[:, idx], ss)
     # chunked == whole over all lanes (ragged split that is not a multiple of the kernel chunk)
     y2 = torch.empty_like(y)
@@ -124,6 +126,7 @@ def test_c3_hbf_dec16_16384_lanes(eng):
     ss = np.zeros((words, idx.size), np.uint32)
     assert o.cfgcall("hbf_int_f32", icfg, ss, xs, ys, idx.size, fi, LM) == 0
     assert H.ulp_diff_f32(yi.cpu().numpy()[idx], ys).max() == 0
+    assert_same_float(ys, yi.cpu().numpy()[idx], "hbf_int_f32, sampled lanes")
     assert np.array_equal(sti.cpu().numpy().view(np.uint32)[:, idx], ss)
     yif = torch.empty((fi, lanes, R), dtype=torch.float32, device=DEV)
     sti2 = torch.zeros_like(sti)
@@ -206,6 +209,7 @@ def test_c5_f32_df2t_one_million_lanes(eng):
     ss = np.zeros((2, idx.size), np.uint32)
     assert o.stream("biquad_f32_df2t", cfg, 1, ss, xs, ys, idx.size, frames, FM) == 0
     assert H.ulp_diff_f32(y[:, tidx].cpu().numpy(), ys).max() == 0  # bar: 0 ULP (allowed: 1)
+    assert_same_float(ys, y[:, tidx].cpu().numpy(), "biquad_f32_df2t, sampled lanes")  # ... and the sign of zero
     assert np.array_equal(st[:, tidx].cpu().numpy().view(np.uint32), ss)
     # 8-way lane split (what each rank of an 8-GPU run computes), LANE_MAJOR shards of 512 frames
     fr = 512

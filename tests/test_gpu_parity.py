@@ -14,6 +14,7 @@ import pytest
 from idsp_amd import _abi
 from tests import _harness as H
 from tests._backends import GpuBackend, OracleBackend
+from tests._float_special import assert_same_float
 
 pytestmark = pytest.mark.gpu
 
@@ -96,6 +97,8 @@ def run_both(bes, op, cfg, n, words, x, lanes, frames, layout, rng, is_float=Fal
         if is_float:
             assert H.ulp_diff_f32(yo, yg).max(initial=0) <= F32_ULP_TOL
             assert H.ulp_diff_f32(so.view(np.float32), sg.view(np.float32)).max(initial=0) <= F32_ULP_TOL
+            assert_same_float(yo, yg, (op, lanes, frames, layout, inplace))  # ... and the sign of zero, NaN against NaN only
+            assert_same_float(so.view(np.float32), sg.view(np.float32), (op, lanes, frames, layout, inplace, "state"))
         else:
             assert np.array_equal(yo, yg)
             assert np.array_equal(so, sg)
@@ -106,6 +109,7 @@ def run_both(bes, op, cfg, n, words, x, lanes, frames, layout, rng, is_float=Fal
         assert rco == 0 and rcg == 0
         if is_float:
             assert H.ulp_diff_f32(yo, yg).max(initial=0) <= F32_ULP_TOL
+            assert_same_float(yo, yg, (op, lanes, frames, layout, inplace, "second call"))
         else:
             assert np.array_equal(yo, yg) and np.array_equal(so, sg)
 
@@ -209,10 +213,12 @@ def test_biquad_f64_parity(bes, op, words, clamp, layout):
             rcg, yg = gb.stream(op, cfg, n, sg, x.copy(), lanes, frames, layout, inplace=inplace)
             assert rco == 0 and rcg == 0, H.engine().err()
             assert H.ulp_diff_f64(yo, yg).max(initial=0) <= F32_ULP_TOL
+            assert_same_float(yo, yg, (op, lanes, frames, layout, inplace))
             assert np.array_equal(so, sg)
             rco, yo = ob.stream(op, cfg, n, so, x[::-1].copy(), lanes, frames, layout)
             rcg, yg = gb.stream(op, cfg, n, sg, x[::-1].copy(), lanes, frames, layout)
             assert H.ulp_diff_f64(yo, yg).max(initial=0) <= F32_ULP_TOL and np.array_equal(so, sg)
+            assert_same_float(yo, yg, (op, lanes, frames, layout, inplace, "second call"))
 
 
 @pytest.mark.parametrize("layout", [FM, LM])
@@ -228,6 +234,7 @@ def test_cascade_f64_parity(bes, layout):
             rcg, yg = gb.stream("cascade_f64_df1", cfg, n, sg, x, lanes, frames, layout)
             assert rco == 0 and rcg == 0
             assert H.ulp_diff_f64(yo, yg).max(initial=0) <= F32_ULP_TOL and np.array_equal(so, sg)
+            assert_same_float(yo, yg, ("cascade_f64_df1", lanes, frames, layout, rep))
         # same samples as n separate DF1 sections
         _, yr = gb.stream("biquad_f64_df1", cfg, n, np.zeros((8 * n, lanes), np.uint32), x, lanes, frames, layout)
         _, yc = gb.stream("cascade_f64_df1", cfg, n, np.zeros((4 + 4 * n, lanes), np.uint32), x, lanes, frames, layout)
@@ -257,6 +264,7 @@ def test_f32_nonfinite_and_denormal_tail(bes):
     _, yg = gb.stream("biquad_f32_df1", cfg, 1, sg, x, 1, x.size, FM)
     assert np.array_equal(np.isnan(yo), np.isnan(yg))
     assert H.ulp_diff_f32(yo, yg).max() == 0
+    assert_same_float(yo, yg, "biquad_f32_df1 on inf / NaN")
 
 
 def test_empty_and_error_paths(bes):
@@ -323,6 +331,8 @@ def test_hbf_parity(bes, kind, layout, tap_set, stages):
             assert rco == 0 and rcg == 0, H.engine().err()
             assert H.ulp_diff_f32(yo, yg).max(initial=0) <= F32_ULP_TOL, (lanes, frames, rep)
             assert H.ulp_diff_f32(so.view(np.float32), sg.view(np.float32)).max(initial=0) <= F32_ULP_TOL
+            assert_same_float(yo, yg, (kind, tap_set, stages, lanes, frames, layout, rep))
+            assert_same_float(so.view(np.float32), sg.view(np.float32), (kind, tap_set, stages, lanes, frames, layout, rep, "state"))
 
 
 @pytest.mark.parametrize("kind", ["dec", "int"])
@@ -342,6 +352,7 @@ def test_hbf_custom_taps_generic_path(bes, kind):
         rc, yg = gb.cfgcall(f"hbf_{kind}_f32", cfg, sg, x, (lanes * nout,), np.float32, lanes, frames, layout)
         assert rc == 0
         assert H.ulp_diff_f32(yo, yg).max() <= F32_ULP_TOL
+        assert_same_float(yo, yg, (kind, "custom taps", layout))
         assert np.array_equal(so, sg)
 
 
@@ -366,6 +377,7 @@ def test_fir_sym_parity(bes, kind, layout):
                 rcg, yg = gb.cfgcall("fir_sym_f32_process", cfg, sg, x, (lanes * frames,), np.float32, lanes, frames, layout)
                 assert rco == 0 and rcg == 0, H.engine().err()
                 assert H.ulp_diff_f32(yo, yg).max(initial=0) <= F32_ULP_TOL
+                assert_same_float(yo, yg, ("fir_sym_f32", kind, m, lanes, frames, layout, rep))
                 assert np.array_equal(so, sg)
 
 
