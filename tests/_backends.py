@@ -60,6 +60,9 @@ class OracleBackend:
 
 
 class GpuBackend:
+    """Every device buffer of a call sits between guard bands (tests/_guard.py).  After the call and the synchronisation the bands
+    of all its buffers are compared with the sentinel, and an input the call must not write (everything except an in-place `x`,
+    the state and `y`) with what was uploaded."""
     name = "hip"
 
     def __init__(self):
@@ -68,42 +71,50 @@ class GpuBackend:
         self.torch = torch
         self.e = H.engine()
         self.dev = torch.device("cuda:0")
+        self.g = None  # the guarded buffers of the call in flight
 
     # IDSP_TEST_MISALIGN=1: every device buffer starts one element (4 or 8 bytes) into its allocation, so the whole parity
     # suite can be replayed on buffers without 16-byte alignment (tests/test_gpu_misaligned.py does that in a subprocess)
-    def _alloc(self, n, dtype):
+    def _off(self, itemsize):
         import os
 
-        if os.environ.get("IDSP_TEST_MISALIGN"):
-            return self.torch.empty(int(n) + 1, dtype=dtype, device=self.dev)[1:]
-        return self.torch.empty(int(n), dtype=dtype, device=self.dev)
+        return int(itemsize) if os.environ.get("IDSP_TEST_MISALIGN") else 0
 
-    def _up(self, a):
+    def _begin(self):
+        from tests._guard import Guards
+
+        self.g = Guards(self.dev)
+
+    def _alloc(self, n, dtype, role="y"):
+        return self.g.empty(role, int(n), dtype, self._off(self.torch.empty(0, dtype=dtype).element_size()))
+
+    def _up(self, a, role, readonly=False):
         if a is None:
             return None
         a = np.ascontiguousarray(a)
-        view = a.view(np.int32) if a.dtype == np.uint32 else a
-        host = self.torch.from_numpy(view.copy())
-        t = self._alloc(host.numel(), host.dtype)
-        t.copy_(host.reshape(-1))
-        return t.reshape(host.shape)
+        return self.g.upload(role, a, self._off(a.dtype.itemsize), readonly)
 
     def _down(self, t, like_dtype):
         a = t.cpu().numpy()
         return a.view(like_dtype) if a.dtype != like_dtype else a
+
+    def _end(self, op):
+        self.torch.cuda.synchronize()
+        self.g.check(op)
 
     def stream(self, op, cfg, n, state, x, lanes, frames, layout, inplace=False):
         import os
 
         torch = self.torch
         inplace = inplace or bool(os.environ.get("IDSP_TEST_INPLACE"))  # `Inplace::inplace` for every stream call
-        xs = self._up(x)
+        self._begin()
+        xs = self._up(x, "x", readonly=not inplace)
         ys = xs if inplace else self._alloc(xs.numel(), xs.dtype).reshape(xs.shape)
         if not inplace:
             ys.fill_(-77 if xs.dtype == torch.int32 else float("nan"))  # poison: every element must be written
-        ss = self._up(state)
+        ss = self._up(state, "state")
         rc = self.e.stream(op, cfg, n, ss, xs, ys, lanes, frames, layout)
-        torch.cuda.synchronize()
+        self._end(op)
         if ss is not None:
             state[...] = self._down(ss, np.uint32).reshape(state.shape)
         return rc, self._down(ys, x.dtype).reshape(np.shape(x))
@@ -113,13 +124,14 @@ class GpuBackend:
 
         torch = self.torch
         inplace = inplace or bool(os.environ.get("IDSP_TEST_INPLACE"))
-        xs, cs, ss = self._up(x), self._up(coef), self._up(state)
+        self._begin()
+        xs, cs, ss = self._up(x, "x", readonly=not inplace), self._up(coef, "coef", readonly=True), self._up(state, "state")
         ys = xs if inplace else self._alloc(xs.numel(), xs.dtype).reshape(xs.shape)
         if not inplace:
             ys.fill_(-77 if xs.dtype == torch.int32 else float("nan"))
         args = (H._ptr(cs),) + (() if frac is None else (frac,)) + (n, H._ptr(ss), H._ptr(xs), H._ptr(ys), lanes, frames, layout, None)
         rc = self.e.fn[op + "_bylane"](*args)
-        torch.cuda.synchronize()
+        self._end(op + "_bylane")
         if ss is not None:
             state[...] = self._down(ss, np.uint32).reshape(state.shape)
         assert np.array_equal(self._down(cs, coef.dtype).reshape(coef.shape), coef)  # coefficients are read-only
@@ -127,38 +139,42 @@ class GpuBackend:
 
     def cfgcall(self, op, cfg, state, x, y_shape, y_dtype, lanes, frames, layout):
         torch = self.torch
-        xs = self._up(x)
+        self._begin()
+        xs = self._up(x, "x", readonly=True)
         tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.int64): torch.int64}.get(np.dtype(y_dtype), torch.int32)
         ys = self._alloc(int(np.prod(y_shape)), tdt)
         ys.fill_(float("nan") if tdt == torch.float32 else -77)  # poison: every element must be written
-        ss = self._up(state)
+        ss = self._up(state, "state")
         rc = self.e.cfgcall(op, cfg, ss, xs, ys, lanes, frames, layout)
-        torch.cuda.synchronize()
+        self._end(op)
         state[...] = self._down(ss, np.uint32).reshape(state.shape)
         return rc, self._down(ys, y_dtype).reshape(y_shape)
 
     def cossin(self, phases):
         torch = self.torch
-        ps = self._up(np.ascontiguousarray(phases, dtype=np.int32))
+        self._begin()
+        ps = self._up(np.ascontiguousarray(phases, dtype=np.int32), "x", readonly=True)
         out = self._alloc(ps.numel() * 2, torch.int32)
         rc = self.e.fn["cossin_i32"](H._ptr(ps), H._ptr(out), ps.numel(), None)
-        torch.cuda.synchronize()
+        self._end("cossin_i32")
         return rc, out.cpu().numpy().reshape(-1, 2)
 
     def atan2(self, xy):
         torch = self.torch
-        xs = self._up(np.ascontiguousarray(xy, dtype=np.int32))
+        self._begin()
+        xs = self._up(np.ascontiguousarray(xy, dtype=np.int32), "x", readonly=True)
         out = self._alloc(xs.numel() // 2, torch.int32)
         rc = self.e.fn["atan2_i32"](H._ptr(xs), H._ptr(out), out.numel(), None)
-        torch.cuda.synchronize()
+        self._end("atan2_i32")
         return rc, out.cpu().numpy()
 
     def dds(self, state, lanes, frames, layout):
         torch = self.torch
-        ss = self._up(state)
+        self._begin()
+        ss = self._up(state, "state")
         out = self._alloc(lanes * frames * 2, torch.int32)
         rc = self.e.fn["dds_i32"](H._ptr(ss), H._ptr(out), lanes, frames, layout, None)
-        torch.cuda.synchronize()
+        self._end("dds_i32")
         state[...] = self._down(ss, np.uint32).reshape(state.shape)
         return rc, out.cpu().numpy()
 

@@ -316,16 +316,16 @@ C3 = {("dec", 16384, FM): "hbf_dec_ring[FrameMajor]", ("dec", 16384, LM): "hbf_d
 
 
 def hbf_cases():
-    """hbf_dec_f32 / hbf_int_f32 for /2 ... /32 and both tap sets on the ring / block shapes of test_gpu_parity.hbf_shapes()
+    """hbf_dec_f32 / hbf_int_f32 for /2 ... /32 and both tap sets on the ring / block shapes of test_gpu_parity.hbf_base_shapes()
     plus 16384 lanes (/16: the C3 kernels); the f64 entries; one custom all-positive tap set per decimator (generic-taps
     kernel; the only way a decimator's kind-1 lanes give -0, the built-in taps alternating in sign)."""
-    from tests.test_gpu_parity import hbf_shapes
+    from tests.test_gpu_parity import hbf_base_shapes
 
     out = []
     for kind in ("dec", "int"):
         for tap_set in (0, 1):
             for stages in (1, 2, 3, 4, 5):
-                shapes = hbf_shapes(stages) + ([(16384, 64)] if stages == 4 and tap_set == 0 else [])
+                shapes = hbf_base_shapes(stages) + ([(16384, 64)] if stages == 4 and tap_set == 0 else [])
                 for lanes, frames in shapes:
                     for layout in (FM, LM):
                         r = 1 << stages

@@ -82,6 +82,7 @@ def test_chunked_calls_continue_the_stream(gpu):
     import torch
 
     from tests import _harness as H
+    from tests._guard import Guards
     from tests.test_gpu_pitch import DEV, init_state, p, sample, tdtype
 
     rng = np.random.default_rng(603)
@@ -94,14 +95,16 @@ def test_chunked_calls_continue_the_stream(gpu):
         o = H.oracle()
         want, so = np.empty_like(xh), st0.copy()
         assert o.stream(op, cfg, n, so, xh, want, lanes, f1 + f2, H.FM) == 0
-        xd = torch.from_numpy(xh).to(DEV)
-        yd = torch.empty_like(xd)
-        sg = torch.from_numpy(st0.view(np.int32)).to(DEV)
+        g = Guards(DEV)  # guard bands around x, y and the state; x is read-only (tests/_guard.py)
+        xd = g.upload("x", xh, readonly=True)
+        yd = g.empty("y", xd.numel(), xd.dtype).reshape(xd.shape)
+        sg = g.upload("state", st0)
         esz = xd.element_size()
         for a, b in ((0, f1), (f1, f1 + f2)):
             rc = gpu.fn[op](C.cast(cfg, C.c_void_p), n, p(sg), C.c_void_p(xd.data_ptr() + a * lanes * esz), C.c_void_p(yd.data_ptr() + a * lanes * esz), lanes, b - a, H.FM, None)
             assert rc == 0 and kernel_of(gpu).startswith(PAIR), (op, kernel_of(gpu))
         torch.cuda.synchronize()
+        g.check((op, "600 + 700 frames"))
         assert np.array_equal(yd.cpu().numpy().view(np.uint8), want.view(np.uint8)), op
         assert np.array_equal(sg.cpu().numpy().view(np.uint32), so), op
 

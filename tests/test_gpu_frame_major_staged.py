@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests import _harness as H
+from tests._guard import Guards
 from tests.test_gpu_pitch import DEV, SENT, cases, init_state, p, sample, tdtype
 
 pytestmark = pytest.mark.gpu
@@ -40,15 +41,19 @@ def run_case(eng, op, cfg, n, words, dt, rng, lanes, frames, pitch, inplace, off
     so = st0.copy()
     assert o.stream(op, cfg, n, so, xh, want, lanes, frames, FM) == 0
     t = tdtype(dt)
-    xb = torch.full((frames * pitch,), SENT, dtype=t, device=DEV)
+    g = Guards(DEV)  # guard bands around x, y and the state; a non-in-place x (padding included) is read-only (tests/_guard.py)
+    xb = g.full("x", frames * pitch, t, SENT)
     xb.view(frames, pitch)[:, off:off + lanes] = torch.from_numpy(xh).to(DEV)
-    yb = xb if inplace else torch.full((frames * pitch,), SENT, dtype=t, device=DEV)
-    sg = torch.from_numpy(st0.view(np.int32)).to(DEV)
+    if not inplace:
+        g.freeze("x")
+    yb = xb if inplace else g.full("y", frames * pitch, t, SENT)
+    sg = g.upload("state", st0)
     esz = xb.element_size()
     rc = eng.fn[op + "_pitch"](C.cast(cfg, C.c_void_p), n, p(sg), C.c_void_p(xb.data_ptr() + off * esz), pitch,
                                C.c_void_p(yb.data_ptr() + off * esz), pitch, lanes, frames, FM, None)
     torch.cuda.synchronize()
     assert rc == 0, (op, eng.err())
+    g.check((op, lanes, frames, pitch, inplace, kernel_of(eng)))
     yv = yb.view(frames, pitch)
     got = yv[:, off:off + lanes].cpu().numpy()
     assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), (op, lanes, frames, pitch, inplace)

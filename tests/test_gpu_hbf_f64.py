@@ -9,29 +9,27 @@ import torch
 
 from idsp_amd import _abi
 from tests import _harness as H
+from tests._guard import Guards
 
 pytestmark = pytest.mark.gpu
 FM, LM = H.FM, H.LM
 DEV = "cuda:0"
 
 
-def dev(a):
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(DEV)
-
-
 def pair(name, cfg, words, nin_of, nout_of, shapes, layout, rng):
     o, e = H.oracle(), H.engine()
     for lanes, frames in shapes:
         st0 = rng.standard_normal((words // 2, lanes)).view(np.uint32).reshape(words // 2, lanes, 2).transpose(0, 2, 1).reshape(words, lanes).copy()
-        so, sg = st0.copy(), dev(st0)
+        g = Guards(DEV)  # every buffer between guard bands, x read-only (tests/_guard.py)
+        so, sg = st0.copy(), g.upload("state", st0)
         for rep in range(2):
             x = rng.standard_normal(lanes * nin_of(frames))
             yo = np.empty(lanes * nout_of(frames))
-            yg = torch.full((yo.size,), float("nan"), dtype=torch.float64, device=DEV)
+            yg = g.full("y", yo.size, torch.float64, float("nan"))
             assert o.cfgcall(name, cfg, so, x, yo, lanes, frames, layout) == 0
-            assert e.cfgcall(name, cfg, sg, dev(x), yg, lanes, frames, layout) == 0, e.err()
+            assert e.cfgcall(name, cfg, sg, g.upload("x", x, readonly=True), yg, lanes, frames, layout) == 0, e.err()
             torch.cuda.synchronize()
+            g.check((name, lanes, frames, layout, rep))
             assert np.array_equal(yg.cpu().numpy().view(np.uint64), yo.view(np.uint64)), (name, lanes, frames, layout, rep)
             assert np.array_equal(sg.cpu().numpy().view(np.uint32), so), (name, lanes, frames, layout, rep)
 

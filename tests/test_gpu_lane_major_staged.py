@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests import _harness as H
+from tests._guard import Guards
 from tests.test_gpu_pitch import DEV, SENT, cases, init_state, p, sample, tdtype
 
 pytestmark = pytest.mark.gpu
@@ -41,13 +42,17 @@ def run_case(eng, op, cfg, n, words, dt, rng, lanes, frames, pitch, inplace):
     so = st0.copy()
     assert o.stream(op, cfg, n, so, xh, want, lanes, frames, LM) == 0
     t = tdtype(dt)
-    xb = torch.full((lanes * pitch,), SENT, dtype=t, device=DEV)
+    g = Guards(DEV)  # guard bands around x, y and the state; a non-in-place x (padding included) is read-only (tests/_guard.py)
+    xb = g.full("x", lanes * pitch, t, SENT)
     xb.view(lanes, pitch)[:, :frames] = torch.from_numpy(xh).to(DEV)
-    yb = xb if inplace else torch.full((lanes * pitch,), SENT, dtype=t, device=DEV)
-    sg = torch.from_numpy(st0.view(np.int32)).to(DEV)
+    if not inplace:
+        g.freeze("x")
+    yb = xb if inplace else g.full("y", lanes * pitch, t, SENT)
+    sg = g.upload("state", st0)
     rc = eng.fn[op + "_pitch"](C.cast(cfg, C.c_void_p), n, p(sg), p(xb), pitch, p(yb), pitch, lanes, frames, LM, None)
     torch.cuda.synchronize()
     assert rc == 0, (op, eng.err())
+    g.check((op, lanes, frames, pitch, inplace, kernel_of(eng)))
     yv = yb.view(lanes, pitch)
     got = yv[:, :frames].cpu().numpy()
     assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), (op, lanes, frames, pitch, inplace)
@@ -125,12 +130,13 @@ def test_unaligned_rows_fall_back_to_the_tile_kernel(gpu):
     want = np.empty_like(xh)
     so = np.zeros((words * n, lanes), np.uint32)
     assert o.stream(op, cfg, n, so, xh, want, lanes, frames, LM) == 0
-    xb = torch.zeros(lanes * frames + 4, dtype=torch.int32, device=DEV)
-    xb[1:1 + lanes * frames] = torch.from_numpy(xh.reshape(-1)).to(DEV)
-    yb = torch.zeros(lanes * frames, dtype=torch.int32, device=DEV)
-    sg = torch.zeros((words * n, lanes), dtype=torch.int32, device=DEV)
-    rc = gpu.fn[op](C.cast(cfg, C.c_void_p), n, p(sg), C.c_void_p(xb.data_ptr() + 4), p(yb), lanes, frames, LM, None)
+    g = Guards(DEV)
+    xb = g.upload("x", xh.reshape(-1), off=4, readonly=True)
+    yb = g.full("y", lanes * frames, torch.int32, 0)
+    sg = g.upload("state", np.zeros((words * n, lanes), np.uint32))
+    rc = gpu.fn[op](C.cast(cfg, C.c_void_p), n, p(sg), p(xb), p(yb), lanes, frames, LM, None)
     torch.cuda.synchronize()
+    g.check((op, lanes, frames, "x 4 bytes off the 16-byte grid"))
     assert rc == 0 and kernel_of(gpu).startswith("stream_lane_major<"), kernel_of(gpu)
     assert np.array_equal(yb.cpu().numpy().reshape(lanes, frames), want)
 

@@ -9,6 +9,7 @@ import torch
 
 from tests import _harness as H
 from tests import _lockin_generic_cases as G
+from tests._guard import Guards
 
 pytestmark = pytest.mark.gpu
 FM, LM = H.FM, H.LM
@@ -24,13 +25,14 @@ def dev(a):
 def run_pair(name, cfg, n, st0, x, lo, ydtype, lanes, frames, layout, lo_form):
     """Run oracle and HIP on the same inputs for two consecutive calls; assert equal outputs and state."""
     o, e = H.oracle(), H.engine()
-    so, sg = st0.copy(), dev(st0)
+    g = Guards(DEV)  # every buffer between guard bands; x and the LO samples are read-only (tests/_guard.py)
+    so, sg = st0.copy(), g.upload("state", st0)
     for rep in range(2):
         yo = np.empty(lanes * frames * 2, ydtype)
-        yg = torch.full((lanes * frames * 2,), -77, dtype=torch.float32 if ydtype == np.float32 else torch.int32, device=DEV)
-        xd = dev(x[rep])
+        yg = g.full("y", lanes * frames * 2, torch.float32 if ydtype == np.float32 else torch.int32, -77)
+        xd = g.upload("x", x[rep], readonly=True)
         if lo_form:
-            lod = dev(lo[rep])
+            lod = g.upload("lo", lo[rep], readonly=True)
             rco = G.call_lo(o, name, cfg, n, so, x[rep], lo[rep], yo, lanes, frames, layout, False)
             rcg = G.call_lo(e, name, cfg, n, sg, xd, lod, yg, lanes, frames, layout, True)
         else:
@@ -38,6 +40,7 @@ def run_pair(name, cfg, n, st0, x, lo, ydtype, lanes, frames, layout, lo_form):
             rcg = e.stream(name, cfg, n, sg, xd, yg, lanes, frames, layout)
         torch.cuda.synchronize()
         assert rco == 0 and rcg == 0, e.err()
+        g.check((name, lanes, frames, layout, rep, e.last_kernel()))
         got = yg.cpu().numpy()
         assert np.array_equal(got.view(np.uint32), yo.view(np.uint32)), (name, lanes, frames, layout, rep, e.last_kernel())
         assert np.array_equal(sg.cpu().numpy().view(np.uint32), so), (name, lanes, frames, layout, rep)

@@ -15,6 +15,7 @@ import torch
 
 from tests import _harness as H
 from tests import _lockin_generic_cases as G
+from tests._guard import Guards
 
 pytestmark = pytest.mark.gpu
 LM = H.LM
@@ -23,9 +24,10 @@ FRAMES = [16, 112, 128, 144, 208, 272, 400]  # 1, 7, 8, 9, 13, 17, 25 batches of
 LANES = [64, 70, 129]
 
 
-def dev(a):
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(DEV)
+def synced(g, e):
+    """Wait for the call, then: no byte outside any buffer of the case changed, inputs as uploaded (tests/_guard.py)."""
+    torch.cuda.synchronize()
+    g.check(e.last_kernel())
 
 
 def is_waves(e):
@@ -42,14 +44,15 @@ def test_lowpass_arms_every_flush_position(gpu, entry, width, ndt, tdt, order, c
     for lanes in LANES:
         for frames in FRAMES:
             st = rng.integers(0, 1 << 32, size=(2 + 4 * order * cascade, lanes), dtype=np.uint64).astype(np.uint32)
-            so, sg = st.copy(), dev(st)
+            g = Guards(DEV)
+            so, sg = st.copy(), g.upload("state", st)
             for rep in range(2):
                 x = rng.integers(-(1 << 31), (1 << 31) - 1, size=lanes * frames, dtype=np.int64).astype(np.int32)
                 yo = np.empty(lanes * frames * width, ndt)
-                yg = torch.full((lanes * frames * width,), -77, dtype=tdt, device=DEV)
+                yg = g.full("y", lanes * frames * width, tdt, -77)
                 assert o.cfgcall(entry, cfg, so, x, yo, lanes, frames, LM) == 0
-                assert e.cfgcall(entry, cfg, sg, dev(x), yg, lanes, frames, LM) == 0, e.err()
-                torch.cuda.synchronize()
+                assert e.cfgcall(entry, cfg, sg, g.upload("x", x, readonly=True), yg, lanes, frames, LM) == 0, e.err()
+                synced(g, e)
                 assert is_waves(e), e.last_kernel()
                 assert np.array_equal(yg.cpu().numpy(), yo), (entry, lanes, frames, rep)
                 assert np.array_equal(sg.cpu().numpy().view(np.uint32), so), (entry, lanes, frames, rep)
@@ -74,17 +77,18 @@ def test_biquad_arms_and_external_lo_every_flush_position(gpu):
                      ("lockin_f32_biquad_lo_process", arrf, 2, rng.standard_normal((16, lanes)).astype(np.float32).view(np.uint32), xf, lof, np.float32)]
             cases[0][3][:2] = rng.integers(0, 1 << 32, (2, lanes), dtype=np.uint64).astype(np.uint32)
             for name, c, n, st0, xs, los, ydt in cases:
-                so, sg = st0.copy(), dev(st0)
+                g = Guards(DEV)
+                so, sg = st0.copy(), g.upload("state", st0)
                 for rep in range(2):
                     yo = np.empty(lanes * frames * 2, ydt)
-                    yg = torch.full((lanes * frames * 2,), -77, dtype=torch.float32 if ydt == np.float32 else torch.int32, device=DEV)
+                    yg = g.full("y", lanes * frames * 2, torch.float32 if ydt == np.float32 else torch.int32, -77)
                     if los is None:
                         rco = o.stream(name, c, n, so, xs[rep], yo, lanes, frames, LM)
-                        rcg = e.stream(name, c, n, sg, dev(xs[rep]), yg, lanes, frames, LM)
+                        rcg = e.stream(name, c, n, sg, g.upload("x", xs[rep], readonly=True), yg, lanes, frames, LM)
                     else:
                         rco = G.call_lo(o, name, c, n, so, xs[rep], los[rep], yo, lanes, frames, LM, False)
-                        rcg = G.call_lo(e, name, c, n, sg, dev(xs[rep]), dev(los[rep]), yg, lanes, frames, LM, True)
-                    torch.cuda.synchronize()
+                        rcg = G.call_lo(e, name, c, n, sg, g.upload("x", xs[rep], readonly=True), g.upload("lo", los[rep], readonly=True), yg, lanes, frames, LM, True)
+                    synced(g, e)
                     assert rco == 0 and rcg == 0, e.err()
                     assert is_waves(e), (name, e.last_kernel())
                     assert np.array_equal(yg.cpu().numpy().view(np.uint32), yo.view(np.uint32)), (name, lanes, frames, rep)
@@ -100,12 +104,13 @@ def test_a_staggered_launch(gpu):
     cfg = H.lockin_cfg([[1 << 22, -(1 << 27)], [1 << 21, -(1 << 26)]])
     st = rng.integers(0, 1 << 32, size=(2 + 4 * 2 * 2, lanes), dtype=np.uint64).astype(np.uint32)
     x = rng.integers(-(1 << 31), (1 << 31) - 1, size=lanes * frames, dtype=np.int64).astype(np.int32)
-    so, sg = st.copy(), dev(st)
+    g = Guards(DEV)
+    so, sg = st.copy(), g.upload("state", st)
     yo = np.empty(lanes * frames * 2, np.int32)
-    yg = torch.full((lanes * frames * 2,), -77, dtype=torch.int32, device=DEV)
+    yg = g.full("y", lanes * frames * 2, torch.int32, -77)
     assert o.cfgcall("lockin_i32_process", cfg, so, x, yo, lanes, frames, LM) == 0
-    assert e.cfgcall("lockin_i32_process", cfg, sg, dev(x), yg, lanes, frames, LM) == 0, e.err()
-    torch.cuda.synchronize()
+    assert e.cfgcall("lockin_i32_process", cfg, sg, g.upload("x", x, readonly=True), yg, lanes, frames, LM) == 0, e.err()
+    synced(g, e)
     assert is_waves(e), e.last_kernel()
     assert np.array_equal(yg.cpu().numpy(), yo) and np.array_equal(sg.cpu().numpy().view(np.uint32), so)
 
@@ -120,14 +125,15 @@ def test_rows_that_are_not_whole_batches(gpu, entry, width, ndt, tdt):
     cfg = H.lockin_cfg([[1 << 22, -(1 << 27)], [1 << 21, -(1 << 26)]])
     for lanes, frames in [(64, 36), (70, 100), (129, 1000), (64, 2076), (200, 44), (64, 28), (64, 34)]:
         st = rng.integers(0, 1 << 32, size=(18, lanes), dtype=np.uint64).astype(np.uint32)
-        so, sg = st.copy(), dev(st)
+        g = Guards(DEV)
+        so, sg = st.copy(), g.upload("state", st)
         for rep in range(2):
             x = rng.integers(-(1 << 31), (1 << 31) - 1, size=lanes * frames, dtype=np.int64).astype(np.int32)
             yo = np.empty(lanes * frames * width, ndt)
-            yg = torch.full((lanes * frames * width,), -77, dtype=tdt, device=DEV)
+            yg = g.full("y", lanes * frames * width, tdt, -77)
             assert o.cfgcall(entry, cfg, so, x, yo, lanes, frames, LM) == 0
-            assert e.cfgcall(entry, cfg, sg, dev(x), yg, lanes, frames, LM) == 0, e.err()
-            torch.cuda.synchronize()
+            assert e.cfgcall(entry, cfg, sg, g.upload("x", x, readonly=True), yg, lanes, frames, LM) == 0, e.err()
+            synced(g, e)
             split = frames >= 32 and frames % 4 == 0
             assert e.last_kernel().startswith("lockin_waves_kernel + stream kernel (last frames % 16)") == split, (e.last_kernel(), frames)
             assert np.array_equal(yg.cpu().numpy(), yo), (entry, lanes, frames, rep)
@@ -144,14 +150,15 @@ def test_biquad_arm_rows_that_are_not_whole_batches(gpu):
             st = np.zeros((2 + 8 * n, lanes), np.uint32)
             st[:2] = rng.integers(0, 1 << 32, (2, lanes), dtype=np.uint64).astype(np.uint32)
             st[2:] = rng.integers(-(1 << 20), 1 << 20, (8 * n, lanes)).astype(np.int32).view(np.uint32)
-            so, sg = st.copy(), dev(st)
+            g = Guards(DEV)
+            so, sg = st.copy(), g.upload("state", st)
             for rep in range(2):
                 x = rng.integers(-(1 << 28), 1 << 28, lanes * frames, dtype=np.int32)
                 yo = np.empty(lanes * frames * 2, np.int32)
-                yg = torch.full((lanes * frames * 2,), -77, dtype=torch.int32, device=DEV)
+                yg = g.full("y", lanes * frames * 2, torch.int32, -77)
                 assert o.stream("lockin_i32_biquad_process", arr, n, so, x, yo, lanes, frames, LM) == 0
-                assert e.stream("lockin_i32_biquad_process", arr, n, sg, dev(x), yg, lanes, frames, LM) == 0, e.err()
-                torch.cuda.synchronize()
+                assert e.stream("lockin_i32_biquad_process", arr, n, sg, g.upload("x", x, readonly=True), yg, lanes, frames, LM) == 0, e.err()
+                synced(g, e)
                 assert e.last_kernel().startswith("lockin_waves_kernel + stream kernel (last frames % 16)") == (frames % 4 == 0), e.last_kernel()
                 assert np.array_equal(yg.cpu().numpy(), yo) and np.array_equal(sg.cpu().numpy().view(np.uint32), so), (n, lanes, frames, rep)
 
@@ -174,13 +181,14 @@ def test_external_lo_rows_that_are_not_whole_batches(gpu):
                  ("lockin_i32_biquad_lo_process", arr, 2, rng.integers(-(1 << 20), 1 << 20, (16, lanes)).astype(np.int32).view(np.uint32), x, lo, np.int32),
                  ("lockin_f32_biquad_lo_process", arrf, 2, rng.standard_normal((16, lanes)).astype(np.float32).view(np.uint32), xf, lof, np.float32)]
         for name, c, n, st0, xs, los, ydt in cases:
-            so, sg = st0.copy(), dev(st0)
+            g = Guards(DEV)
+            so, sg = st0.copy(), g.upload("state", st0)
             for rep in range(2):
                 yo = np.empty(lanes * frames * 2, ydt)
-                yg = torch.full((lanes * frames * 2,), -77, dtype=torch.float32 if ydt == np.float32 else torch.int32, device=DEV)
+                yg = g.full("y", lanes * frames * 2, torch.float32 if ydt == np.float32 else torch.int32, -77)
                 rco = G.call_lo(o, name, c, n, so, xs[rep], los[rep], yo, lanes, frames, LM, False)
-                rcg = G.call_lo(e, name, c, n, sg, dev(xs[rep]), dev(los[rep]), yg, lanes, frames, LM, True)
-                torch.cuda.synchronize()
+                rcg = G.call_lo(e, name, c, n, sg, g.upload("x", xs[rep], readonly=True), g.upload("lo", los[rep], readonly=True), yg, lanes, frames, LM, True)
+                synced(g, e)
                 assert rco == 0 and rcg == 0, e.err()
                 assert np.array_equal(yg.cpu().numpy().view(np.uint32), yo.view(np.uint32)), (name, lanes, frames, rep, e.last_kernel())
                 assert np.array_equal(sg.cpu().numpy().view(np.uint32), so), (name, lanes, frames, rep)

@@ -14,15 +14,12 @@ import pytest
 import torch
 
 from tests import _harness as H
+from tests._guard import Guards
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = (("lockin_i32_process", 2, np.int32, torch.int32), ("lockin_i32_arg", 1, np.int32, torch.int32),
            ("lockin_i32_norm_sqr", 1, np.int64, torch.int64))
-
-
-def _dev(a):
-    return torch.from_numpy(a).cuda()
 
 
 def _one(o, e, rng, name, width, ndt, tdt, lanes, frames, order, split, expect):
@@ -34,8 +31,9 @@ def _one(o, e, rng, name, width, ndt, tdt, lanes, frames, order, split, expect):
     so = st.copy()
     yo = np.empty(lanes * frames * width, ndt)
     assert o.cfgcall(name, cfg, so, x, yo, lanes, frames, H.FM) == 0
-    sg, xv = _dev(st.view(np.int32).copy()), _dev(x)
-    yv = torch.zeros(yo.size, dtype=tdt, device="cuda")
+    g = Guards()  # every buffer between guard bands, x read-only (tests/_guard.py)
+    sg, xv = g.upload("state", st), g.upload("x", x, readonly=True)
+    yv = g.full("y", yo.size, tdt, 0)
     parts = [(0, frames)] if split is None else [(0, split), (split, frames)]
     for f0, f1 in parts:
         assert e.cfgcall(name, cfg, sg, xv[f0 * lanes:f1 * lanes], yv[f0 * lanes * width:f1 * lanes * width], lanes, f1 - f0, H.FM) == 0, e.err()
@@ -43,6 +41,7 @@ def _one(o, e, rng, name, width, ndt, tdt, lanes, frames, order, split, expect):
             assert expect in e.last_kernel(), (e.last_kernel(), name, lanes, f1 - f0)
     torch.cuda.synchronize()
     ctx = (name, lanes, frames, order, split)
+    g.check(ctx)
     assert np.array_equal(yv.cpu().numpy(), yo), ctx
     assert np.array_equal(sg.cpu().numpy().view(np.uint32), so), ctx
 

@@ -297,42 +297,169 @@ def _cascade(kind, tap_set, stages):
     return cfg
 
 
-HBF_CASES = [(_cascade, 0, s) for s in (1, 2, 3, 4, 5)] + [(_cascade, 1, s) for s in (2, 4, 5)]
+HBF_CASES = [(_cascade, 0, s) for s in (1, 2, 3, 4, 5)] + [(_cascade, 1, s) for s in (1, 2, 3, 4, 5)]
 
 
-def hbf_shapes(stages):
+def hbf_base_shapes(stages):
+    """(lanes, frames) per kernel family.  Also the shapes of the special-value tables (tests/_float_special.py), whose per-case
+    conditions (INF_LOST among them) are worked out for exactly these."""
     ch = 4096 >> stages
+    rnd = 1024 >> stages  # output frames of one round / chunk of 1024 high-rate samples
     return [(1, 1), (3, 5), (2, ch - 1), (2, ch), (3, ch + 1), (1, 2 * ch + 7), (17, 40),
             (4, 1), (4, ch + 3), (8, 130), (12, 2 * ch + 5), (20, 70),  # whole 4-lane workgroups: FM block kernel
             # whole 16-lane groups: the FM ring kernel (/16); rounds of 1024 input samples: one, ragged, the first / last two (SAFE) and FAST ones
-            (64, 3 * (1024 >> stages) + 1), (16, 1), (16, (1024 >> stages) - 1), (48, 2 * (1024 >> stages) + 5), (16, 7 * (1024 >> stages) + 3),
+            (64, 3 * rnd + 1), (16, 1), (16, rnd - 1), (48, 2 * rnd + 5), (16, 7 * rnd + 3),
             # LM blocked kernel (hbf_blk.h): stage s >= 2 runs every 2^(s-1) rounds of 1024 input samples — whole runs, a flushed
             # partial run behind them, two runs of the deepest stage (/32: 8 rounds) and a ragged tail
-            (3, 9 * (1024 >> stages)), (2, 6 * (1024 >> stages) + 4), (2, 17 * (1024 >> stages) + 2)]
+            (3, 9 * rnd), (2, 6 * rnd + 4), (2, 17 * rnd + 2)]
+
+
+def hbf_shapes(stages):
+    """The half-band parity shapes: those above and the ragged group counts."""
+    rnd = 1024 >> stages
+    return hbf_base_shapes(stages) + [
+            # ragged group counts: the group kernels give XCD b % 8 the groups (b % 8) * ceil(ngroups / 8) + b / 8 and drop those past
+            # the end (hbf_ring.h:434, hbf_wave.h block kernels).  9 and 13 four-lane groups (FM block kernels), 9 and 11 sixteen-lane
+            # groups (/16 ring), 29 one-lane blocks in a grid of 32 (wave kernels, four per XCD); one full round and a ragged one
+        (36, rnd + 3), (52, rnd + 3), (144, rnd + 3), (176, rnd + 3), (29, rnd + 3)]
+
+
+# ---- launch_hbf restated (idsp_amd/csrc/hbf.hip:576-598 and the launch_* it calls): which kernel a call must take -------------------
+HBF_M = ((23, 10, 5, 4, 3), (15, 6, 3, 3, 2))  # hbf_taps.h kHbfM: taps of tuple entry t, tap sets 0 / 1; stage s of an S-stage
+#                                                decimator is entry S - 1 - s, of an interpolator entry s (hbf_tuple_index)
+HBF_GENERIC = {"dec": "hbf_dec_kernel (generic taps)", "int": "hbf_int_kernel (generic taps)"}
+HBF_LDS_LIMIT = 160 * 1024
+
+
+def _up4(v):
+    return (v + 3) & ~3
+
+
+def hbf_casc_lds_words(tap_set, stages, dec):
+    """`Casc<TS, S, DEC>::lds_words` (hbf_wave.h:80-100) with kCH = 1024, kSlack = 8: stream A (+ stream B of a decimator) per stage."""
+    words = 0
+    for s in range(stages):
+        m = HBF_M[tap_set][stages - 1 - s if dec else s]
+        if dec:
+            n = 1024 >> (s + 1)
+            words += _up4(_up4(m - 1) + n + 8) + _up4(_up4(2 * m - 1) + n + 8)
+        else:
+            n = (1024 >> stages) << s
+            words += _up4(_up4(2 * m - 1) + n + 8)
+    return words
+
+
+def hbf_block_fm_bytes(tap_set, stages, dec):
+    """Dynamic LDS of `hbf_dec_block_fm` / `hbf_int_block_fm` (hbf_wave.h:682,696): kBlkLanes = 4 cascades and the output tile."""
+    tile = 2 * (1024 >> stages) * 4 if dec else 4 * 1024
+    return (4 * _up4(hbf_casc_lds_words(tap_set, stages, dec)) + tile) * 4
+
+
+def hbf_expected_kernel(builtin, kind, layout, tap_set, stages, lanes, frames, wide_aligned):
+    """Start of `idsp_last_kernel()` for idsp_hbf_{dec,int}_f32.  `frames`: the call's frame count (low-rate frames); `wide_aligned`:
+    the high-rate buffer (x of a decimator, y of an interpolator) starts on a 16-byte boundary.
+
+    hbf.hip:576-598    fast paths only for a built-in tap set, an aligned wide buffer and LaneMajor rows of whole 16-byte pieces
+                       (frames * R % 4 == 0) / FrameMajor frames of at least 16 bytes (R >= 4); decimators try blk, ring, wave in turn
+    hbf_blk.h:446-464  blk: every LaneMajor decimator (lanes < 2^31)
+    hbf_ring.h:579-595 ring: FrameMajor, /16 with M(0) <= 4 (both tap sets: 4 and 3), whole 16-lane groups
+    hbf_wave.h:668-714 LaneMajor: interpolators only (int_wave); FrameMajor from 2 stages: block_fm on whole 4-lane groups if its LDS
+                       is at most 160 KiB, else the wave-per-lane kernel; 1 stage FrameMajor: not handled
+    The 160 KiB condition excludes no instance: `test_hbf_block_fm_lds_table` holds the largest, dec tap set 0 /32, to 36352 bytes."""
+    dec, lm, rate = kind == "dec", layout == LM, 1 << stages
+    if builtin and wide_aligned and ((frames * rate) % 4 == 0 if lm else rate >= 4):
+        if dec and lm:
+            return "hbf_dec_blk[LaneMajor]"
+        if dec and stages == 4 and HBF_M[tap_set][3] <= 4 and lanes % 16 == 0:
+            return "hbf_dec_ring[FrameMajor]"
+        if lm:
+            return "hbf_int_wave[LaneMajor]"
+        if stages >= 2:
+            if hbf_block_fm_bytes(tap_set, stages, dec) <= HBF_LDS_LIMIT and lanes % 4 == 0:
+                return f"hbf_{kind}_block_fm"
+            return f"hbf_{kind}_wave[FrameMajor]"
+    return HBF_GENERIC[kind]
+
+
+def test_hbf_block_fm_lds_table():
+    """The `bytes <= 160 KiB` conditions of the two block kernels, per (tap set, stages): which instances they exclude.  None."""
+    table = {(dec, ts, s): hbf_block_fm_bytes(ts, s, dec) for dec in (True, False) for ts in (0, 1) for s in (2, 3, 4, 5)}
+    assert hbf_casc_lds_words(0, 4, True) == 2116  # the figure hbf_wave.h quotes for the /16 decimator's per-lane region
+    assert table[(True, 0, 5)] == max(table.values()) == 36352
+    assert all(b <= HBF_LDS_LIMIT for b in table.values()), table
+
+
+HBF_SEEN = {}   # (kind, layout) -> kernel names the parametrised run reached (default dispatch only)
+HBF_RAN = set()  # the cases of test_hbf_parity that completed under default dispatch
+HBF_CENSUS = {
+    ("dec", LM): {"hbf_dec_blk[LaneMajor]", HBF_GENERIC["dec"]},
+    ("dec", FM): {"hbf_dec_ring[FrameMajor]", "hbf_dec_block_fm", "hbf_dec_wave[FrameMajor]", HBF_GENERIC["dec"]},
+    ("int", LM): {"hbf_int_wave[LaneMajor]", HBF_GENERIC["int"]},
+    ("int", FM): {"hbf_int_block_fm", "hbf_int_wave[FrameMajor]", HBF_GENERIC["int"]},
+}
 
 
 @pytest.mark.parametrize("tap_set,stages", [(c[1], c[2]) for c in HBF_CASES])
 @pytest.mark.parametrize("layout", [LM, FM])
 @pytest.mark.parametrize("kind", ["dec", "int"])
 def test_hbf_parity(bes, kind, layout, tap_set, stages):
+    import os
+
     ob, gb = bes
     cfg = _cascade(kind, tap_set, stages)
     R = 1 << stages
     words = H.oracle().fn[f"hbf_{kind}_state_words"](C.byref(cfg))
     rng = np.random.default_rng(1000 * stages + 10 * tap_set + layout)
+    # IDSP_DIAG lets the environment override the dispatch: then only the name is not asserted.  Buffers one element into their
+    # allocation (IDSP_TEST_MISALIGN) are off the 16-byte grid: the generic kernel
+    pinned, aligned = not os.environ.get("IDSP_DIAG"), not os.environ.get("IDSP_TEST_MISALIGN")
     for lanes, frames in hbf_shapes(stages):
         init = rng.standard_normal(size=(words, lanes)).astype(np.float32).view(np.uint32)
         so, sg = init.copy(), init.copy()
         nin, nout = (frames * R, frames) if kind == "dec" else (frames, frames * R)
+        want = hbf_expected_kernel(True, kind, layout, tap_set, stages, lanes, frames, aligned)
         for rep in range(2):  # second call continues from the written-back history
             x = adversarial_f32(rng, lanes * nin)
             rco, yo = ob.cfgcall(f"hbf_{kind}_f32", cfg, so, x, (lanes * nout,), np.float32, lanes, frames, layout)
             rcg, yg = gb.cfgcall(f"hbf_{kind}_f32", cfg, sg, x, (lanes * nout,), np.float32, lanes, frames, layout)
             assert rco == 0 and rcg == 0, H.engine().err()
+            took = H.engine().last_kernel()
+            if pinned:
+                assert took.startswith(want), (took, want, kind, tap_set, stages, lanes, frames, layout)
+                if aligned:
+                    HBF_SEEN.setdefault((kind, layout), set()).add(want)
             assert H.ulp_diff_f32(yo, yg).max(initial=0) <= F32_ULP_TOL, (lanes, frames, rep)
             assert H.ulp_diff_f32(so.view(np.float32), sg.view(np.float32)).max(initial=0) <= F32_ULP_TOL
             assert_same_float(yo, yg, (kind, tap_set, stages, lanes, frames, layout, rep))
             assert_same_float(so.view(np.float32), sg.view(np.float32), (kind, tap_set, stages, lanes, frames, layout, rep, "state"))
+    if pinned and aligned:
+        HBF_RAN.add((kind, layout, tap_set, stages))
+
+
+def test_hbf_census_per_kind_and_layout():
+    """The kernels `test_hbf_parity` reaches, per (kind, layout): exactly those of HBF_CENSUS -- ring only at /16.  The restatement
+    must give that set for the cases and shapes of the run, and, when the whole parametrised run came before this test under
+    default dispatch (each call's name asserted there), so must the names the engine reported."""
+    import os
+
+    for (kind, layout), census in HBF_CENSUS.items():
+        names, ring_stages = set(), set()
+        for _, tap_set, stages in HBF_CASES:
+            for lanes, frames in hbf_shapes(stages):
+                k = hbf_expected_kernel(True, kind, layout, tap_set, stages, lanes, frames, True)
+                names.add(k)
+                if "ring" in k:
+                    ring_stages.add(stages)
+                if k == HBF_GENERIC[kind] and layout == FM:
+                    assert stages == 1, (kind, tap_set, stages, lanes, frames)
+        assert names == census, (kind, layout, names)
+        assert ring_stages == ({4} if (kind, layout) == ("dec", FM) else set())
+    if os.environ.get("IDSP_DIAG") or os.environ.get("IDSP_TEST_MISALIGN"):
+        return  # dispatch overridden / every buffer off the 16-byte grid: test_hbf_parity asserts no census names there
+    every = {(kind, layout, ts, s) for kind in ("dec", "int") for layout in (LM, FM) for _, ts, s in HBF_CASES}
+    if HBF_RAN != every:
+        pytest.skip("parametrised run of test_hbf_parity incomplete: the restated census holds, the reached one was not compared")
+    assert HBF_SEEN == HBF_CENSUS, HBF_SEEN
 
 
 @pytest.mark.parametrize("kind", ["dec", "int"])

@@ -18,6 +18,7 @@ from idsp_amd import _abi
 from idsp_amd._abi import PHASE  # the feature's prototype table
 from tests import _harness as H
 from tests import _phase_spec as S
+from tests._guard import Guards
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -71,21 +72,25 @@ def gpu_run(gpu, form, ba, st, x, layout, inplace=False, chunks=None):
     """x [frames, lanes] int32 (numpy); st [words, lanes] uint32, updated; returns the output as [frames, lanes(, 2)].
     chunks: frame counts of consecutive calls on one state (their sum = frames)."""
     frames, lanes = x.shape
-    sd = torch.from_numpy(st.view(np.int32).copy()).to(DEV)
+    gs = Guards(DEV)  # the state of all chunks; every buffer sits between guard bands (tests/_guard.py)
+    sd = gs.upload("state", st)
     outs = []
     f0 = 0
     for n in chunks or [frames]:
-        xd = torch.from_numpy(to_layout(x[f0:f0 + n], layout)).to(DEV)
+        g = Guards(DEV)
+        xd = g.upload("x", to_layout(x[f0:f0 + n], layout), readonly=not inplace)
         if inplace:
             assert form in FOUR_BYTE
             yd = xd
         elif form == "unwrap1":
-            yd = torch.full((lanes * n,), POISON, dtype=torch.int64, device=DEV)
+            yd = g.full("y", lanes * n, torch.int64, POISON)
         else:
-            yd = torch.full((lanes * n * (2 if form == "pll2" else 1),), POISON, dtype=torch.int32, device=DEV)
+            yd = g.full("y", lanes * n * (2 if form == "pll2" else 1), torch.int32, POISON)
         gpu_call(gpu, form, ba, sd, xd, yd, lanes, n, layout)
         torch.cuda.synchronize()
         KERNELS[(form, layout, lanes, n)] = gpu.last_kernel()
+        g.check((form, layout, lanes, n, KERNELS[(form, layout, lanes, n)]))
+        gs.check((form, layout, lanes, n, KERNELS[(form, layout, lanes, n)]))
         y = yd.cpu().numpy()
         if form == "pll2":
             y = y.reshape(-1, 2)
@@ -182,16 +187,20 @@ def test_reference_convergence_tests(gpu, name, chunk):
     lib_ba = (C.c_int32 * 3)()
     assert gpu.fn["pll_from_bandwidth"](k["bandwidth"], k["split"], lib_ba) == 0 and list(lib_ba) == ba
     ss, sg = np.zeros((9, lanes), np.uint32), np.zeros((9, lanes), np.uint32)
-    sd = torch.from_numpy(sg.view(np.int32)).to(DEV)
+    gs = Guards(DEV)
+    sd = gs.upload("state", sg)
     worst_f = worst_p = 0
     for f0 in range(0, n, chunk):
         idx = np.arange(f0 + 1, f0 + chunk + 1, dtype=np.uint64)[:, None]  # Accu: pre-increment (src/accu.rs:34-37)
         x = ((idx * step[None, :] + np.uint64(k["accu_state"])) & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
         want = S.pll_np(ba, ss, x, output=2)
-        xd = torch.from_numpy(x).to(DEV)
-        yd = torch.full((chunk * lanes * 2,), POISON, dtype=torch.int32, device=DEV)
+        g = Guards(DEV)
+        xd = g.upload("x", x, readonly=True)
+        yd = g.full("y", chunk * lanes * 2, torch.int32, POISON)
         gpu_call(gpu, "pll2", ba, sd, xd, yd, lanes, chunk, H.FM)
         torch.cuda.synchronize()
+        g.check((name, f0))
+        gs.check((name, f0))
         got = yd.cpu().numpy().reshape(chunk, lanes, 2)
         assert np.array_equal(got, want), (name, f0)
         sel = np.arange(f0, f0 + chunk) > k["bounds_apply_for_i_greater_than"]
@@ -224,14 +233,16 @@ def test_lockin_arg_into_pll_frequency(gpu):
     ps = np.zeros((9, lanes), np.uint32)
     want = S.pll_np(ba, ps, arg_o, output=1)
 
-    sd = torch.from_numpy(st.view(np.int32).copy()).to(DEV)
-    xd = torch.from_numpy(tone).to(DEV)
-    ad = torch.full((frames * lanes,), POISON, dtype=torch.int32, device=DEV)
+    g = Guards(DEV)
+    sd = g.upload("lock-in state", st)
+    xd = g.upload("x", tone, readonly=True)
+    ad = g.full("arg", frames * lanes, torch.int32, POISON)
     assert gpu.cfgcall("lockin_i32_arg", lc, sd, xd, ad, lanes, frames, H.FM) == 0, gpu.err()
-    pd = torch.zeros((9, lanes), dtype=torch.int32, device=DEV)
-    fd = torch.full((frames * lanes,), POISON, dtype=torch.int32, device=DEV)
+    pd = g.full("pll state", 9 * lanes, torch.int32, 0).reshape(9, lanes)
+    fd = g.full("y", frames * lanes, torch.int32, POISON)
     gpu_call(gpu, "pll1", ba, pd, ad, fd, lanes, frames, H.FM)
     torch.cuda.synchronize()
+    g.check("lockin_i32_arg -> pll_i32")
     assert np.array_equal(ad.cpu().numpy().reshape(frames, lanes), arg_o)
     got = fd.cpu().numpy().reshape(frames, lanes)
     assert np.array_equal(got, want) and np.array_equal(pd.cpu().numpy().view(np.uint32), ps)
