@@ -63,6 +63,14 @@ class FirSymF32(C.Structure):
     _fields_ = [("kind", C.c_int32), ("m", C.c_int32), ("taps", C.c_float * HBF_MAX_TAPS)]
 
 
+PFB_MAX_TAPS = 16  # IDSP_PFB_MAX_TAPS
+
+
+class PfbF32(C.Structure):
+    """idsp_pfb_f32: coeff[tap][m] = prototype[tap*4 + m]"""
+    _fields_ = [("taps", C.c_int32), ("dft", C.c_int32), ("coeff", (C.c_float * 4) * PFB_MAX_TAPS)]
+
+
 class HbfCascadeF64(C.Structure):
     _fields_ = [
         ("stages", C.c_int32),
@@ -308,6 +316,15 @@ PHASE = {
     "pll_from_bandwidth": (_I, [_D, _D, _P]),
 }
 UTILS.update(PHASE)
+
+# polyphase channelizer (product only, no twin in the checker library: parity rests on tests/_pfb_spec.py); merged into UTILS
+# the way PHASE is
+PFB = {
+    "pfb_state_words": (_SZ, [_P]),
+    "pfb_prototype_f32": (_I, [_I, _P]),
+    "pfb_f32_process": (_I, [_P, _P, _P, _P, _SZ, _SZ, _I, _P]),  # cfg, state, x, y, lanes, frames, layout, stream
+}
+UTILS.update(PFB)
 
 SHARD_FN = C.CFUNCTYPE(_I, _P, _I, _SZ, _SZ, _P)  # idsp_shard_fn
 

@@ -23,6 +23,7 @@ own:
     Split::stateful(Cic::new(rate)).decimate() (cic.rs:338) Cic(N, rate).decimate().lanes(n)
     PLL / PLLState                       (pll.rs:33-107)  PLL.from_bandwidth(bw, split).lanes(N, output=...)
     Unwrapper<i64> / ClampWrap<W<i32>>   (unwrap.rs:109-194) Unwrapper().lanes(N), ClampWrap().lanes(N)
+    PolyphaseBank (* Dft4), prototype()  (examples/polyphase_channelizer.rs) PolyphaseBank.prototype(taps).lanes(N)
     overflowing_sub / saturating_scale   (unwrap.rs:73-101) overflowing_sub(y, x), saturating_scale(lo, hi, shift)
     cossin(phase)                        (cossin.rs:14)  cossin(phases)
     atan2(y, x) / Complex::arg           (atan2.rs:66)   atan2(xy)
@@ -47,7 +48,7 @@ __all__ = [
     "FrameMajor", "LaneMajor", "View", "ViewMut", "Biquad", "BiquadClamp", "Cascade",
     "DirectForm1", "DirectForm2Transposed", "DirectForm1Wide", "DirectForm1Dither", "DirectForm",
     "Split", "Lanes", "ByLane", "HbfDecCascade", "HbfIntCascade", "FirSym", "Cic", "Normal", "Wdf", "HBF_TAPS", "HBF_TAPS_98",
-    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "FmDisc", "PLL", "Unwrapper", "ClampWrap", "overflowing_sub", "saturating_scale", "cossin", "atan2", "sos", "sos_clamp_wide", "IdspError",
+    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "FmDisc", "PLL", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "sos", "sos_clamp_wide", "IdspError",
 ]
 
 FrameMajor = _abi.FRAME_MAJOR  # dsp-process/src/view.rs:10
@@ -1017,6 +1018,49 @@ class ClampWrapLanes(_LaneOp):
     def _run(self, x, y, frames, layout):
         call("clamp_wrap_i32", C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
              self.n_lanes, frames, layout, _stream_ptr(x))
+
+
+class PolyphaseBank(_LaneOp):
+    """`PolyphaseBank` (examples/polyphase_channelizer.rs:52-75), followed by `Dft4` (:77-101) when `dft` (the `.minor()`
+    tuple of :107-109), as `SplitProcess<Frame, Frame, BankState>`: a four-channel maximally decimated polyphase analysis
+    bank.  The element is a `Frame` = `[[f32; 2]; 4]`: FrameMajor tensors are [frames, lanes, 4, 2], views have width 8.
+    `coeff[tap][m]` is `prototype[tap*4 + m]` (:104); 1..16 taps."""
+
+    dtype_in = dtype_out = torch.float32
+    in_width = out_width = 8
+
+    def __init__(self, coeff: Sequence[Sequence[float]], dft: bool = True):
+        load()
+        if not 1 <= len(coeff) <= _abi.PFB_MAX_TAPS or any(len(row) != 4 for row in coeff):
+            raise ValueError("coeff is [[f32; 4]; TAPS] with 1..16 taps")
+        self.cfg = _abi.PfbF32()
+        self.cfg.taps, self.cfg.dft = len(coeff), 1 if dft else 0
+        for t, row in enumerate(coeff):
+            for m, v in enumerate(row):
+                self.cfg.coeff[t][m] = v
+
+    @classmethod
+    def prototype(cls, taps: int = 8, dft: bool = True) -> "PolyphaseBank":
+        """`prototype()` (:33-44) for 4 * taps coefficients, cast to `[[f32; 4]; TAPS]` (:104)."""
+        cfg = _abi.PfbF32()
+        call("pfb_prototype_f32", taps, C.byref(cfg))
+        return cls([[cfg.coeff[t][m] for m in range(4)] for t in range(taps)], dft)
+
+    @property
+    def coeff(self) -> List[List[float]]:
+        return [[self.cfg.coeff[t][m] for m in range(4)] for t in range(self.cfg.taps)]
+
+    def lanes(self, n: int, device="cuda") -> "PolyphaseBank":
+        _LaneOp.__init__(self, n, call("pfb_state_words", C.byref(self.cfg)), device)
+        return self
+
+    def head(self) -> torch.Tensor:
+        """`BankState::head` of every lane (:49)."""
+        return self.state[8 * self.cfg.taps]
+
+    def _run(self, x, y, frames, layout):
+        call("pfb_f32_process", C.byref(self.cfg), C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()),
+             C.c_void_p(y.data_ptr()), self.n_lanes, frames, layout, _stream_ptr(x))
 
 
 def cossin(p: torch.Tensor) -> torch.Tensor:

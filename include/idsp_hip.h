@@ -822,6 +822,40 @@ int idsp_pll_from_zpk(double zero, double pole, double gain, int32_t ba[3]);
 int idsp_pll_from_bandwidth(double bw, double split, int32_t ba[3]);
 
 /* ------------------------------------------------------------------------ */
+/* four-channel polyphase channelizer (examples/polyphase_channelizer.rs)   */
+/* ------------------------------------------------------------------------ */
+/*
+ * A maximally decimated polyphase FIR bank on complex f32 frames, optionally followed by a 4-point DFT.  One lane is one
+ * independent input stream with its own `BankState` (:46-50).  The element of x and of y is a `Frame` = `[[f32; 2]; 4]` (:22-25),
+ * 8 floats `[m][re, im]`, under the convention of the `[f32; R]` elements of idsp_hbf_dec_f32:
+ *   FRAME_MAJOR x[(f*lanes + l)*8 + k],  LANE_MAJOR x[(l*frames + f)*8 + k];  `frames` counts frames (4 input samples each).
+ * Per frame, `PolyphaseBank::process` (:57-75): head = (head + taps - 1) % taps; hist[head] = x; y = +0.0; then for tap = 0 .. taps
+ * in that order, for each m and each of re / im: y[m][c] = y[m][c] + hist[(head + tap) % taps][m][c] * coeff[tap][m] — one IEEE
+ * multiply, then one IEEE add, never fused.  dft = 1 hands y to `Dft4::process` (:80-100, the eight sums as written, left to
+ * right): the `.minor()` tuple of :107.  M stays 4, the only size `Dft4` defines an order of additions for.
+ * State: 8*taps + 1 words per lane, state[w*lanes + lane]: word (slot*4 + m)*2 + c is `hist[slot][m][c]` in the reference's
+ * physical slot order, word 8*taps is `head`; all zero is `Default`.  Read at entry and written at exit: chunked calls equal
+ * one long call bit for bit, in y and in every state word.  A head >= taps is a caller error; it is taken modulo taps.
+ * y == x is allowed (same-rate operator); any other overlap of x and y is IDSP_EINVAL, as are taps outside
+ * 1..IDSP_PFB_MAX_TAPS, a dft other than 0 / 1, a bad layout, NULL pointers with work to do and an x or y that is not 16-byte
+ * aligned.  lanes == 0 or frames == 0 launches nothing, as for idsp_fir_sym_f32_process.
+ */
+#define IDSP_PFB_MAX_TAPS 16
+typedef struct idsp_pfb_f32 {
+    int32_t taps;                        /* 1..IDSP_PFB_MAX_TAPS (`TAPS`, :20: 8) */
+    int32_t dft;                         /* 0: `PolyphaseBank` alone (:57-75), 1: `PolyphaseBank` -> `Dft4` (:80-100, :107-109) */
+    float coeff[IDSP_PFB_MAX_TAPS][4];   /* coeff[tap][m] = prototype[tap*4 + m] (`bytemuck::cast`, :104) */
+} idsp_pfb_f32;
+/* 8*taps + 1 (`BankState`, :46-50); 0 for an invalid configuration. */
+size_t idsp_pfb_state_words(const idsp_pfb_f32 *cfg);
+/* `prototype()` (:29-44) for 4*taps coefficients: a Hamming-windowed sinc at 0.9 of the channel spacing, normalised to a sum of
+ * one; f32 throughout in the reference's order of operations.  Sets taps and dft = 1.  Host code, no GPU needed. */
+int idsp_pfb_prototype_f32(int taps, idsp_pfb_f32 *out);
+/* `PolyphaseBank::process` (:57-75), then `Dft4::process` (:80-100) when cfg->dft, over `frames` frames of every lane. */
+int idsp_pfb_f32_process(const idsp_pfb_f32 *cfg, void *state, const float *x, float *y, size_t lanes, size_t frames, int layout,
+                         void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* lane split over several devices in ONE process: idsp_multi_*             */
 /* ------------------------------------------------------------------------ */
 /*

@@ -939,6 +939,54 @@ inline int32_t saturating_scale(int32_t lo, int32_t hi, uint32_t shift)
     return int32_t(uint32_t(int64_t(lo) >> shift) + uint32_t(uint64_t(int64_t(hi)) << (32 - shift)));
 }
 
+// ------------------------------------------------------ polyphase channelizer
+/// `PolyphaseBank` (examples/polyphase_channelizer.rs:52-75), followed by `Dft4` (:77-101) when `dft` (the `.minor()` tuple of
+/// :107-109), over `lanes` independent streams, each with its own `BankState` (zero words = `Default`).  The element of both
+/// views is a `Frame` = `[[f32; 2]; 4]`: build them with width 8.
+class PolyphaseBank {
+public:
+    /// `coeff[tap][m]` = `prototype[tap*4 + m]` (`bytemuck::cast`, :104), 1..16 taps
+    PolyphaseBank(const std::vector<std::array<float, 4>> &coeff, bool dft, size_t lanes, void *stream = nullptr)
+        : lanes_(lanes), stream_(stream)
+    {
+        require(!coeff.empty() && coeff.size() <= IDSP_PFB_MAX_TAPS, "1..16 taps");
+        cfg_.taps = int32_t(coeff.size()), cfg_.dft = dft ? 1 : 0;
+        for (size_t t = 0; t < coeff.size(); t++)
+            for (size_t m = 0; m < 4; m++) cfg_.coeff[t][m] = coeff[t][m];
+        state_ = DeviceBuffer<uint32_t>(idsp_pfb_state_words(&cfg_) * lanes);
+    }
+    /// the reference's own bank: `prototype()` (:33-44) for 4 * taps coefficients
+    static PolyphaseBank prototype(int taps, bool dft, size_t lanes, void *stream = nullptr)
+    {
+        idsp_pfb_f32 c{};
+        check(idsp_pfb_prototype_f32(taps, &c));
+        std::vector<std::array<float, 4>> coeff(size_t(c.taps));
+        for (size_t t = 0; t < coeff.size(); t++)
+            for (size_t m = 0; m < 4; m++) coeff[t][m] = c.coeff[t][m];
+        return PolyphaseBank(coeff, dft, lanes, stream);
+    }
+    const idsp_pfb_f32 &config() const { return cfg_; }
+    DeviceBuffer<uint32_t> &state() { return state_; }
+    /// y may be x (`Inplace`)
+    template <class Layout>
+    void process_view(View<float, Layout> x, ViewMut<float, Layout> y)
+    {
+        require(x.frames == y.frames && x.lanes == lanes_ && y.lanes == lanes_, "view shape mismatch");
+        check(idsp_pfb_f32_process(&cfg_, state_.data(), x.flat, y.flat, lanes_, x.frames, Layout::value, stream_));
+    }
+    template <class Layout>
+    void inplace_view(ViewMut<float, Layout> xy)
+    {
+        process_view(View<float, Layout>{xy.flat, xy.frames, xy.lanes}, xy);
+    }
+
+private:
+    idsp_pfb_f32 cfg_{};
+    size_t lanes_;
+    void *stream_;
+    DeviceBuffer<uint32_t> state_;
+};
+
 class PLLLanes;
 /// `PLL { ba: [Q32<32>; 3] }` (src/pll.rs:33-58); the builders run in f32 inside the library, in the reference's order.
 struct PLL {

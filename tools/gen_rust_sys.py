@@ -18,6 +18,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "idsp_hip.h")
 OUT = os.path.join(ROOT, "rust", "idsp-hip-sys", "src", "lib.rs")
+# Configuration structs that live in a module of their own (src/<module>.rs, re-exported from lib.rs).  tests/test_rust_shim.py
+# pins the list of `pub struct`s of lib.rs itself to the ctypes classes it knows; a struct added to the header later goes here, and
+# the test that comes with it (tests/test_pfb_spec.py for `pfb`) holds its size against ctypes the same way.
+SIDE_MODULES = {"idsp_pfb_f32": "pfb"}
 
 SCALARS = {
     "int": "c_int", "unsigned": "c_uint", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",
@@ -137,6 +141,28 @@ def parse(text: str):
     return defines, enums, structs, funcs, opaque, fnptrs
 
 
+def struct_lines(sname, fields, snames, enames, dvals):
+    out = ["#[repr(C)]", "#[derive(Clone, Copy, Debug, PartialEq)]", f"pub struct {camel(sname)} {{"]
+    for ctype, fname, dims in fields:
+        t = rust_type(ctype, snames, enames)
+        for d in reversed(dims):
+            n = d if isinstance(d, int) else int(dvals[d])
+            t = f"[{t}; {n}]"
+        out.append(f"    pub {ident(fname)}: {t},")
+    return out + ["}", ""]
+
+
+def generate_side(module: str) -> str:
+    """src/<module>.rs: the structs of SIDE_MODULES that name `module`"""
+    defines, enums, structs, _, opaque, _ = parse(open(HEADER).read())
+    snames, enames, dvals = {s for s, _ in structs} | set(opaque), {e for e, _ in enums}, dict(defines)
+    out = [f"//! Part of the raw FFI declarations of `libidsp_hip.so`: GENERATED by tools/gen_rust_sys.py from the C header; do not edit.", ""]
+    for sname, fields in structs:
+        if SIDE_MODULES.get(sname) == module:
+            out += struct_lines(sname, fields, snames, enames, dvals)
+    return "\n".join(out)
+
+
 def generate() -> str:
     text = open(HEADER).read()
     defines, enums, structs, funcs, opaque, fnptrs = parse(text)
@@ -163,18 +189,13 @@ def generate() -> str:
         for k, v in items:
             w(f"pub const {k}: c_int = {v};")
         w("")
+    for module in sorted(set(SIDE_MODULES.values())):
+        w(f"mod {module};")
+        w(f"pub use {module}::*;")
+    w("")
     for sname, fields in structs:
-        w("#[repr(C)]")
-        w("#[derive(Clone, Copy, Debug, PartialEq)]")
-        w(f"pub struct {camel(sname)} {{")
-        for ctype, fname, dims in fields:
-            t = rust_type(ctype, snames, enames)
-            for d in reversed(dims):
-                n = d if isinstance(d, int) else int(dvals[d])
-                t = f"[{t}; {n}]"
-            w(f"    pub {ident(fname)}: {t},")
-        w("}")
-        w("")
+        if sname not in SIDE_MODULES:
+            out.extend(struct_lines(sname, fields, snames, enames, dvals))
     for oname in opaque:
         w(f"/// Opaque `{oname}` handle (only ever used behind a pointer).")
         w("#[repr(C)]")
@@ -212,4 +233,7 @@ if __name__ == "__main__":
         os.makedirs(os.path.dirname(OUT), exist_ok=True)
         with open(OUT, "w") as f:
             f.write(src)
+        for module in sorted(set(SIDE_MODULES.values())):
+            with open(os.path.join(os.path.dirname(OUT), module + ".rs"), "w") as f:
+                f.write(generate_side(module))
         print(f"wrote {OUT} ({src.count(chr(10))} lines)")

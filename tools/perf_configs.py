@@ -401,6 +401,32 @@ def phase(op, lanes, frames, layout, iters, tag):
            dispatch=call("last_kernel").decode())
 
 
+def pfb(taps, dft, lanes, frames, layout, iters, tag, inplace=False):
+    """The polyphase channelizer (idsp_pfb_f32_process) beside idsp_device_copy of the same bytes on the same buffers (how bench.py
+    obtains copy_gbs), alternating.  In place the copy goes to a second buffer: it still moves the bytes the kernel reads and writes."""
+    x = torch.randn(lanes * frames * 8, dtype=torch.float32, device=dev)
+    y = torch.empty_like(x)
+    cfg = _abi.PfbF32()
+    call("pfb_prototype_f32", taps, C.byref(cfg))
+    cfg.dft = dft
+    st = torch.zeros((call("pfb_state_words", C.byref(cfg)), lanes), dtype=torch.int32, device=dev)
+    out = x if inplace else y
+
+    def run():
+        call("pfb_f32_process", C.byref(cfg), p(st), p(x), p(out), lanes, frames, layout, sptr())
+
+    def copy():
+        call("device_copy", p(y), p(x), x.numel() * 4, sptr())
+
+    cm, cn = timeit(copy, iters)
+    med, mn = timeit(run, iters)
+    cm2, cn2 = timeit(copy, iters)
+    med2, mn2 = timeit(run, iters)
+    cm, med, mn = min(cm, cm2), min(med, med2), min(mn, mn2)
+    report(f"{tag}:pfb taps {taps} dft {dft} {'LM' if layout else 'FM'} {lanes}x{frames}{' in place' if inplace else ''}", lanes * frames, "frame",
+           64 * lanes * frames, med, mn, copy_ms_median=round(cm, 4), times_copy=round(med / cm, 3), dispatch=call("last_kernel").decode())
+
+
 def copy_ref(nbytes, iters):
     a = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     b = torch.empty_like(a)
@@ -564,6 +590,12 @@ def main():
                 phase("pll_frequency", 65536, 4096, layout, it, "ph")
                 phase("unwrap_phase", 65536, 4096, layout, it, "ph")
             lowpass(2, 2, 65536, 4096, FM, it, "ph")
+    if want("pfb"):  # the channelizer at taps = 8, dft = 1: 2 GiB in / 2 GiB out in both layouts, out of place and in place; the time-split case
+        for layout in (FM, LM):
+            for inplace in (False, True):
+                pfb(8, 1, 16384, 4096, layout, it, "pfb", inplace)
+        pfb(8, 1, 64, 1 << 20, FM, it, "pfb")
+        pfb(8, 1, 64, 1 << 20, LM, it, "pfb")
     if want("lockinc"):  # `Lockin<C>` with biquad arms at the C4 shape (thread-per-lane stream kernels)
         for layout in (FM, LM):
             lockin_generic("phase", 1, 32768, 4096, layout, it, "C4g")
