@@ -326,6 +326,21 @@ PFB = {
 }
 UTILS.update(PFB)
 
+# CORDIC family (product only, no twin in the checker library: parity rests on tests/_cordic_spec.py); merged into UTILS the way
+# PHASE and PFB are
+_CORDIC_SIG = [_P, _P, _P, _SZ, _P]  # xy, z (or NULL), out, n, stream
+CORDIC = {
+    "cordic_cos_sin_i32": (_I, _CORDIC_SIG),
+    "cordic_sqrt_atan2_i32": (_I, _CORDIC_SIG),
+    "cordic_cosh_sinh_i32": (_I, _CORDIC_SIG),
+    "cordic_sqrt_atanh2_i32": (_I, _CORDIC_SIG),
+    "cordic_mul_i32": (_I, _CORDIC_SIG),
+    "cordic_div_i32": (_I, _CORDIC_SIG),
+    "cordic_circular_gain": (_D, []),
+    "cordic_hyperbolic_gain": (_D, []),
+}
+UTILS.update(CORDIC)
+
 SHARD_FN = C.CFUNCTYPE(_I, _P, _I, _SZ, _SZ, _P)  # idsp_shard_fn
 
 

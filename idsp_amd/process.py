@@ -27,6 +27,7 @@ own:
     overflowing_sub / saturating_scale   (unwrap.rs:73-101) overflowing_sub(y, x), saturating_scale(lo, hi, shift)
     cossin(phase)                        (cossin.rs:14)  cossin(phases)
     atan2(y, x) / Complex::arg           (atan2.rs:66)   atan2(xy)
+    cordic::{cos_sin, sqrt_atan2, ...}   (cordic.rs:80-107) cordic_cos_sin(xy, z), cordic_sqrt_atan2(xy, z), ...
 
 Buffers are torch tensors on the GPU (torch is plumbing: device memory and
 streams); every call goes through the C ABI of ``libidsp_hip.so`` on the
@@ -48,7 +49,8 @@ __all__ = [
     "FrameMajor", "LaneMajor", "View", "ViewMut", "Biquad", "BiquadClamp", "Cascade",
     "DirectForm1", "DirectForm2Transposed", "DirectForm1Wide", "DirectForm1Dither", "DirectForm",
     "Split", "Lanes", "ByLane", "HbfDecCascade", "HbfIntCascade", "FirSym", "Cic", "Normal", "Wdf", "HBF_TAPS", "HBF_TAPS_98",
-    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "FmDisc", "PLL", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "sos", "sos_clamp_wide", "IdspError",
+    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "FmDisc", "PLL", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
+    "cordic_circular_gain", "cordic_hyperbolic_gain", "sos", "sos_clamp_wide", "IdspError",
 ]
 
 FrameMajor = _abi.FRAME_MAJOR  # dsp-process/src/view.rs:10
@@ -1081,6 +1083,70 @@ def atan2(xy: torch.Tensor) -> torch.Tensor:
     out = torch.empty(xy.shape[0], dtype=torch.int32, device=xy.device)
     call("atan2_i32", C.c_void_p(xy.data_ptr()), C.c_void_p(out.data_ptr()), out.numel(), _stream_ptr(xy))
     return out
+
+
+def _cordic(entry: str, pair: bool, xy: torch.Tensor, z: Optional[torch.Tensor], out: Optional[torch.Tensor]) -> torch.Tensor:
+    """The shared front of the six CORDIC functions (src/cordic.rs:80-107): xy int32 [..., 2], z int32 of shape xy.shape[:-1] or
+    None (= 0), out int32 of the result's shape or None (allocated).  Everything is validated before the launch."""
+    _check(xy, torch.int32, "xy")
+    if xy.dim() < 1 or xy.shape[-1] != 2:
+        raise ValueError("xy must have shape [..., 2]")
+    lead = tuple(xy.shape[:-1])
+    if z is not None:
+        _check(z, torch.int32, "z")
+        if tuple(z.shape) != lead or z.device != xy.device:
+            raise ValueError(f"z must have shape {lead} on xy's device")
+    shape = lead + (2,) if pair else lead
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=xy.device)
+    else:
+        _check(out, torch.int32, "out")
+        if tuple(out.shape) != shape or out.device != xy.device:
+            raise ValueError(f"out must have shape {shape} on xy's device")
+    call(entry, C.c_void_p(xy.data_ptr()), C.c_void_p(z.data_ptr() if z is not None else None), C.c_void_p(out.data_ptr()),
+         xy.numel() // 2, _stream_ptr(xy))
+    return out
+
+
+def cordic_cos_sin(xy: torch.Tensor, z: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`cos_sin(x, y, z)` (src/cordic.rs:80-82): rows `[x, y]` rotated by `z` turns (2^31 = pi), times the circular gain.
+    out may be xy."""
+    return _cordic("cordic_cos_sin_i32", True, xy, z, out)
+
+
+def cordic_sqrt_atan2(xy: torch.Tensor, z: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`sqrt_atan2(x, y, z)` (src/cordic.rs:85-87): rows `[gain * |x + iy|, z + arg / pi]`.  out may be xy."""
+    return _cordic("cordic_sqrt_atan2_i32", True, xy, z, out)
+
+
+def cordic_cosh_sinh(xy: torch.Tensor, z: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`cosh_sinh(x, y, z)` (src/cordic.rs:100-102), z in units of 2^-31, times the hyperbolic gain.  out may be xy."""
+    return _cordic("cordic_cosh_sinh_i32", True, xy, z, out)
+
+
+def cordic_sqrt_atanh2(xy: torch.Tensor, z: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`sqrt_atanh2(x, y, z)` (src/cordic.rs:105-107): rows `[gain * sqrt(x^2 - y^2), z + atanh(y / x)]`.  out may be xy."""
+    return _cordic("cordic_sqrt_atanh2_i32", True, xy, z, out)
+
+
+def cordic_mul(xy: torch.Tensor, z: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`mul(x, y, z)` (src/cordic.rs:90-92): words `y + x * z`, z in Q31.  out may be z."""
+    return _cordic("cordic_mul_i32", False, xy, z, out)
+
+
+def cordic_div(xy: torch.Tensor, z: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`div(x, y, z)` (src/cordic.rs:95-97): words `z + y / x` in Q31.  out may be z."""
+    return _cordic("cordic_div_i32", False, xy, z, out)
+
+
+def cordic_circular_gain() -> float:
+    """`CORDIC_CIRCULAR_GAIN` (build.rs:80)"""
+    return call("cordic_circular_gain")
+
+
+def cordic_hyperbolic_gain() -> float:
+    """`CORDIC_HYPERBOLIC_GAIN` (build.rs:92-104)"""
+    return call("cordic_hyperbolic_gain")
 
 
 def sos(sos_rows: Sequence[Sequence[float]], xy: torch.Tensor, lanes: int = 1, layout: int = LaneMajor):

@@ -856,6 +856,39 @@ int idsp_pfb_f32_process(const idsp_pfb_f32 *cfg, void *state, const float *x, f
                          void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* CORDIC family (src/cordic.rs)                                            */
+/* ------------------------------------------------------------------------ */
+/*
+ * `cordic::<VECTORING, COORD>(x, y, z, None)` (src/cordic.rs:13-77) elementwise: 30 table entries, every +, - and negation of x, y
+ * and z wrapping (release build), `>>` arithmetic.  Pre-rotation (:25-34): vectoring flips when x < 0, rotating when
+ * z.wrapping_sub(i32::MIN >> 1) < 0; a flip negates x and y and subtracts i32::MIN from z.  Sigma (:55): vectoring y <= 0,
+ * rotating z >= 0.  Hyperbolic mode shifts by i = j + 1 for table entry j and runs the micro-rotation twice at i = 4 and at
+ * i = 13 (:43-52); linear mode computes its angle as (0x80000000u32 >> j) as i32 and leaves x alone (:39-41).
+ * xy: n rows [x, y] (`Complex<i32>`, 8-byte aligned); z: n words, or NULL for z = 0 in every element.  The pair functions
+ * write n rows [first, second] of the reference's tuple, mul and div write n words:
+ *   cos_sin     (:80-82)    [F*(x cos(pi z) - y sin(pi z)), F*(x sin(pi z) + y cos(pi z))]
+ *   sqrt_atan2  (:85-87)    [F*sqrt(x^2 + y^2), z + atan2(y, x)/pi]
+ *   cosh_sinh   (:100-102)  [G*(x cosh z + y sinh z), G*(x sinh z + y cosh z)]
+ *   sqrt_atanh2 (:105-107)  [G*sqrt(x^2 - y^2), z + atanh2(y, x)]
+ *   mul         (:90-92)    y + x*z          div (:95-97)  z + y/x
+ * with F = idsp_cordic_circular_gain(), G = idsp_cordic_hyperbolic_gain() (build.rs:80, :92-104), angles of the circular
+ * functions in turns (2^31 = pi) and of the hyperbolic ones in units of 2^-31.  The functions are elementwise: one call serves
+ * FRAME_MAJOR and LANE_MAJOR buffers alike, such as the `Complex<i32>` output of idsp_lockin_i32_process or idsp_dds_i32.
+ * In place: out == xy for the four pair functions, out == z for mul and div; any other overlap of out with an input is
+ * IDSP_EINVAL, as are a NULL xy or out with n > 0 and an xy or pair out that is not 8-byte aligned.  n == 0 returns IDSP_OK
+ * before any pointer check, as idsp_atan2_i32.
+ */
+int idsp_cordic_cos_sin_i32(const int32_t *xy, const int32_t *z, int32_t *out, size_t n, void *stream);
+int idsp_cordic_sqrt_atan2_i32(const int32_t *xy, const int32_t *z, int32_t *out, size_t n, void *stream);
+int idsp_cordic_cosh_sinh_i32(const int32_t *xy, const int32_t *z, int32_t *out, size_t n, void *stream);
+int idsp_cordic_sqrt_atanh2_i32(const int32_t *xy, const int32_t *z, int32_t *out, size_t n, void *stream);
+int idsp_cordic_mul_i32(const int32_t *xy, const int32_t *z, int32_t *out, size_t n, void *stream);
+int idsp_cordic_div_i32(const int32_t *xy, const int32_t *z, int32_t *out, size_t n, void *stream);
+/* `CORDIC_CIRCULAR_GAIN` (build.rs:80) and `CORDIC_HYPERBOLIC_GAIN` (build.rs:92-104).  Host code, no GPU needed. */
+double idsp_cordic_circular_gain(void);
+double idsp_cordic_hyperbolic_gain(void);
+
+/* ------------------------------------------------------------------------ */
 /* lane split over several devices in ONE process: idsp_multi_*             */
 /* ------------------------------------------------------------------------ */
 /*

@@ -21,6 +21,7 @@
 //   Split::stateful(Cic::new(rate)).decimate()/.interpolate() (cic.rs:338-346)  CicDecimator<T> / CicInterpolator<T>
 //   cossin(phase)                       (cossin.rs:14)          cossin(phases, out)
 //   atan2(y, x) / Complex::arg          (atan2.rs:66)           atan2(xy, out)
+//   cordic::{cos_sin, sqrt_atan2, ...}  (cordic.rs:80-107)      cordic::cos_sin(xy, z, out), cordic::sqrt_atan2(xy, z, out), ...
 //   PLL / PLLState                      (pll.rs:33-107)         PLL::from_bandwidth(bw, split).lanes(n)
 //   Unwrapper<i64> / ClampWrap<W<i32>>  (unwrap.rs:109-194)     Unwrapper(n) / ClampWrap(n)
 //   overflowing_sub / saturating_scale  (unwrap.rs:73-101)      overflowing_sub(y, x) / saturating_scale(lo, hi, shift)
@@ -868,6 +869,86 @@ inline void atan2(const DeviceBuffer<int32_t> &xy, DeviceBuffer<int32_t> &out, v
     require(xy.len() == 2 * out.len(), "xy.len() != 2 * out.len()");
     check(idsp_atan2_i32(xy.data(), out.data(), out.len(), stream));
 }
+
+/// The CORDIC family (src/cordic.rs:80-107): xy holds rows `[x, y]`, z one word per row; the overloads without z take z = 0 for
+/// every row (the C entry's NULL).  The pair functions write rows `[first, second]` of the reference's tuple (out may be xy), mul
+/// and div one word per row (out may be z).
+namespace cordic {
+namespace detail {
+using Entry = int (*)(const int32_t *, const int32_t *, int32_t *, size_t, void *);
+inline void run(Entry f, bool pair, const DeviceBuffer<int32_t> &xy, const DeviceBuffer<int32_t> *z, DeviceBuffer<int32_t> &out, void *stream)
+{
+    require(xy.len() % 2 == 0, "xy.len() is odd");
+    const size_t n = xy.len() / 2;
+    require(!z || z->len() == n, "z.len() != xy.len() / 2");
+    require(out.len() == (pair ? 2 * n : n), pair ? "out.len() != xy.len()" : "out.len() != xy.len() / 2");
+    check(f(xy.data(), z ? z->data() : nullptr, out.data(), n, stream));
+}
+}  // namespace detail
+/// `cos_sin(x, y, z)` (src/cordic.rs:80-82)
+inline void cos_sin(const DeviceBuffer<int32_t> &xy, const DeviceBuffer<int32_t> &z, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_cos_sin_i32, true, xy, &z, out, stream);
+}
+/// `cos_sin(x, y, 0)`
+inline void cos_sin(const DeviceBuffer<int32_t> &xy, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_cos_sin_i32, true, xy, nullptr, out, stream);
+}
+/// `sqrt_atan2(x, y, z)` (src/cordic.rs:85-87)
+inline void sqrt_atan2(const DeviceBuffer<int32_t> &xy, const DeviceBuffer<int32_t> &z, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_sqrt_atan2_i32, true, xy, &z, out, stream);
+}
+/// `sqrt_atan2(x, y, 0)`
+inline void sqrt_atan2(const DeviceBuffer<int32_t> &xy, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_sqrt_atan2_i32, true, xy, nullptr, out, stream);
+}
+/// `mul(x, y, z)` (src/cordic.rs:90-92)
+inline void mul(const DeviceBuffer<int32_t> &xy, const DeviceBuffer<int32_t> &z, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_mul_i32, false, xy, &z, out, stream);
+}
+/// `mul(x, y, 0)`
+inline void mul(const DeviceBuffer<int32_t> &xy, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_mul_i32, false, xy, nullptr, out, stream);
+}
+/// `div(x, y, z)` (src/cordic.rs:95-97)
+inline void div(const DeviceBuffer<int32_t> &xy, const DeviceBuffer<int32_t> &z, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_div_i32, false, xy, &z, out, stream);
+}
+/// `div(x, y, 0)`
+inline void div(const DeviceBuffer<int32_t> &xy, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_div_i32, false, xy, nullptr, out, stream);
+}
+/// `cosh_sinh(x, y, z)` (src/cordic.rs:100-102)
+inline void cosh_sinh(const DeviceBuffer<int32_t> &xy, const DeviceBuffer<int32_t> &z, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_cosh_sinh_i32, true, xy, &z, out, stream);
+}
+/// `cosh_sinh(x, y, 0)`
+inline void cosh_sinh(const DeviceBuffer<int32_t> &xy, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_cosh_sinh_i32, true, xy, nullptr, out, stream);
+}
+/// `sqrt_atanh2(x, y, z)` (src/cordic.rs:105-107)
+inline void sqrt_atanh2(const DeviceBuffer<int32_t> &xy, const DeviceBuffer<int32_t> &z, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_sqrt_atanh2_i32, true, xy, &z, out, stream);
+}
+/// `sqrt_atanh2(x, y, 0)`
+inline void sqrt_atanh2(const DeviceBuffer<int32_t> &xy, DeviceBuffer<int32_t> &out, void *stream = nullptr)
+{
+    detail::run(idsp_cordic_sqrt_atanh2_i32, true, xy, nullptr, out, stream);
+}
+/// `CORDIC_CIRCULAR_GAIN`, `CORDIC_HYPERBOLIC_GAIN` (build.rs:80, :92-104)
+inline double circular_gain() { return idsp_cordic_circular_gain(); }
+inline double hyperbolic_gain() { return idsp_cordic_hyperbolic_gain(); }
+}  // namespace cordic
 
 /// `Lockin<[Lowpass<N>; K]>` fed by a per-lane `Accu<Wrapping<i32>>` (src/lockin.rs:30-39).
 template <int N, int K>

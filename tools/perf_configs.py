@@ -427,6 +427,32 @@ def pfb(taps, dft, lanes, frames, layout, iters, tag, inplace=False):
            64 * lanes * frames, med, mn, copy_ms_median=round(cm, 4), times_copy=round(med / cm, 3), dispatch=call("last_kernel").decode())
 
 
+def cordic(n, iters, tag):
+    """The six CORDIC functions (idsp_cordic_*_i32) with z and with z = NULL at n elements, beside idsp_device_copy of the same
+    bytes and idsp_atan2_i32 at the same n in the same run."""
+    xy = torch.randint(-(1 << 31), (1 << 31) - 1, (2 * n,), dtype=torch.int32, device=dev)
+    z = torch.randint(-(1 << 31), (1 << 31) - 1, (n,), dtype=torch.int32, device=dev)
+    out = torch.empty(2 * n, dtype=torch.int32, device=dev)
+    scratch = torch.empty(6 * n, dtype=torch.int32, device=dev)  # copy source (from word 0) and destination (from word 3 n) of up to 10 n bytes each
+
+    am, an = timeit(lambda: call("atan2_i32", p(xy), p(out), n, sptr()), iters)
+    report(f"{tag}:atan2 {n}", n, "element", 12 * n, am, an, dispatch=call("last_kernel").decode())
+    for name, pair in (("cos_sin", True), ("sqrt_atan2", True), ("cosh_sinh", True), ("sqrt_atanh2", True), ("mul", False), ("div", False)):
+        for zz in (z, None):
+            nbytes = (8 + (4 if zz is not None else 0) + (8 if pair else 4)) * n  # read + written
+
+            def run():
+                call(f"cordic_{name}_i32", p(xy), p(zz) if zz is not None else None, p(out), n, sptr())
+
+            def copy():  # nbytes / 2 copied = nbytes moved
+                call("device_copy", p(scratch[3 * n:]), p(scratch), nbytes // 2, sptr())
+
+            cm, _ = timeit(copy, iters)
+            med, mn = timeit(run, iters)
+            report(f"{tag}:{name}{'' if zz is not None else ' z=NULL'} {n}", n, "element", nbytes, med, mn, copy_ms_median=round(cm, 4),
+                   times_copy=round(med / cm, 3), atan2_ms_median=round(am, 4), times_atan2=round(med / am, 3), dispatch=call("last_kernel").decode())
+
+
 def copy_ref(nbytes, iters):
     a = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     b = torch.empty_like(a)
@@ -596,6 +622,8 @@ def main():
                 pfb(8, 1, 16384, 4096, layout, it, "pfb", inplace)
         pfb(8, 1, 64, 1 << 20, FM, it, "pfb")
         pfb(8, 1, 64, 1 << 20, LM, it, "pfb")
+    if want("cordic"):  # the CORDIC family at 2^26 elements with and without z, beside a copy of the same bytes and atan2 at the same n
+        cordic(1 << 26, it, "cordic")
     if want("lockinc"):  # `Lockin<C>` with biquad arms at the C4 shape (thread-per-lane stream kernels)
         for layout in (FM, LM):
             lockin_generic("phase", 1, 32768, 4096, layout, it, "C4g")
