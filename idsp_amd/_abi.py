@@ -341,6 +341,26 @@ CORDIC = {
 }
 UTILS.update(CORDIC)
 
+# exponential swept sine (product only, no twin in the checker library: parity rests on tests/_sweep_spec.py); merged into UTILS
+# the way PHASE and CORDIC are
+SWEEP_STATE_WORDS = 7  # IDSP_SWEEP_STATE_WORDS: state lo, hi, accu lo, hi, rate, emitted lo, hi
+_I32 = C.c_int32
+_I64 = C.c_int64
+SWEEP = {
+    "sweep_state_words": (_SZ, []),
+    "sweep_i32": (_I, [_P, _P, _SZ, _SZ, _I, _P]),  # state, out, lanes, frames, layout, stream
+    "sweep_fit": (_I, [_D, _D, _D, C.POINTER(_I32), C.POINTER(_I64)]),  # stop, harmonics, cycles (narrowed to f32), rate, state
+    "sweep_rate": (_D, [_I32]),
+    "sweep_delay": (_D, [_I32, _D]),
+    "sweep_octave": (_D, [_I32]),
+    "sweep_decade": (_D, [_I32]),
+    "sweep_cycles": (_D, [_I32, _I64]),
+    "sweep_state": (_D, [_I32, _I64]),
+    "sweep_continuous": (_D, [_I32, _I64, _D]),
+    "sweep_inverse_filter": (_I, [_I32, _I64, _D, _P]),
+}
+UTILS.update(SWEEP)
+
 SHARD_FN = C.CFUNCTYPE(_I, _P, _I, _SZ, _SZ, _P)  # idsp_shard_fn
 
 

@@ -25,6 +25,7 @@ own:
     Unwrapper<i64> / ClampWrap<W<i32>>   (unwrap.rs:109-194) Unwrapper().lanes(N), ClampWrap().lanes(N)
     PolyphaseBank (* Dft4), prototype()  (examples/polyphase_channelizer.rs) PolyphaseBank.prototype(taps).lanes(N)
     overflowing_sub / saturating_scale   (unwrap.rs:73-101) overflowing_sub(y, x), saturating_scale(lo, hi, shift)
+    Sweep / AccuOsc<Sweep>               (sweptsine.rs:12-188) Sweep.fit(stop, harmonics, cycles), SweepOsc(N, rate, state)
     cossin(phase)                        (cossin.rs:14)  cossin(phases)
     atan2(y, x) / Complex::arg           (atan2.rs:66)   atan2(xy)
     cordic::{cos_sin, sqrt_atan2, ...}   (cordic.rs:80-107) cordic_cos_sin(xy, z), cordic_sqrt_atan2(xy, z), ...
@@ -49,7 +50,7 @@ __all__ = [
     "FrameMajor", "LaneMajor", "View", "ViewMut", "Biquad", "BiquadClamp", "Cascade",
     "DirectForm1", "DirectForm2Transposed", "DirectForm1Wide", "DirectForm1Dither", "DirectForm",
     "Split", "Lanes", "ByLane", "HbfDecCascade", "HbfIntCascade", "FirSym", "Cic", "Normal", "Wdf", "HBF_TAPS", "HBF_TAPS_98",
-    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "FmDisc", "PLL", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
+    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "Sweep", "SweepOsc", "FmDisc", "PLL", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
     "cordic_circular_gain", "cordic_hyperbolic_gain", "sos", "sos_clamp_wide", "IdspError",
 ]
 
@@ -856,6 +857,88 @@ class Dds:
         call("dds_i32", C.c_void_p(self.state.data_ptr()), C.c_void_p(out.data_ptr()), self.n_lanes, frames, layout,
              _stream_ptr(out))
         return out
+
+
+class Sweep:
+    """`Sweep { rate: i32, state: i64 }` (src/sweptsine.rs:12-19): `fit` and the descriptors are host calls, no GPU needed."""
+
+    def __init__(self, rate: int, state: int):
+        self.rate, self.state = int(rate), int(state)
+
+    def __repr__(self):
+        return f"Sweep(rate={self.rate:#x}, state={self.state:#x})"
+
+    @classmethod
+    def fit(cls, stop: float, harmonics: float, cycles: float) -> "Sweep":
+        """`Sweep::fit` (:108-118, f32); `SweepError` -> ValueError("Stop out of bounds" / "Start out of bounds")."""
+        fn, _ = load()
+        rate, state = C.c_int32(), C.c_int64()
+        if fn["sweep_fit"](stop, harmonics, cycles, C.byref(rate), C.byref(state)) < 0:
+            raise ValueError(fn["last_error"]().decode(errors="replace"))
+        return cls(rate.value, state.value)
+
+    def rate_(self) -> float:
+        """`Sweep::rate()` (:43-45) — `rate` itself is the field"""
+        return call("sweep_rate", self.rate)
+
+    def delay(self, harmonic: float) -> float:
+        return call("sweep_delay", self.rate, harmonic)
+
+    def octave(self) -> float:
+        return call("sweep_octave", self.rate)
+
+    def decade(self) -> float:
+        return call("sweep_decade", self.rate)
+
+    def cycles(self) -> float:
+        return call("sweep_cycles", self.rate, self.state)
+
+    def state_(self) -> float:
+        """`Sweep::state()` (:67-69) — `state` itself is the field"""
+        return call("sweep_state", self.rate, self.state)
+
+    def continuous(self, t: float) -> float:
+        return call("sweep_continuous", self.rate, self.state, t)
+
+    def inverse_filter(self, f: float) -> complex:
+        out = (C.c_float * 2)()
+        call("sweep_inverse_filter", self.rate, self.state, f, C.cast(out, C.c_void_p))
+        return complex(out[0], out[1])
+
+
+def _i64_words(v, n, device):
+    """per-lane i64 (a scalar or a tensor) -> (lo, hi) int32 tensors"""
+    if isinstance(v, torch.Tensor):
+        t = v.to(device=device, dtype=torch.int64).reshape(n)
+    else:
+        t = torch.tensor([((int(v) + (1 << 63)) % (1 << 64)) - (1 << 63)], dtype=torch.int64).expand(n).contiguous().to(device)
+    return t.to(torch.int32), (t >> 32).to(torch.int32)
+
+
+class SweepOsc:
+    """Per-lane `AccuOsc<Sweep>` (src/sweptsine.rs:160-188) with `Osc` for `W<i32>`: `rate` and `state` per lane as a scalar or a
+    tensor (or one `Sweep` for every lane).  A lane whose `Sweep` has ended writes (0, 0) and keeps its state."""
+
+    def __init__(self, n_lanes: int, rate, state=None, device="cuda"):
+        load()
+        self.n_lanes, self.device = int(n_lanes), torch.device(device)
+        self.state = torch.zeros((_abi.SWEEP_STATE_WORDS, self.n_lanes), dtype=torch.int32, device=self.device)
+        if isinstance(rate, Sweep):
+            rate, state = rate.rate, rate.state
+        self.state[0], self.state[1] = _i64_words(state, self.n_lanes, self.device)  # accu = 0, emitted = 0
+        self.state[4] = _to_i32_tensor(rate, self.n_lanes, self.device)
+
+    def generate(self, out: torch.Tensor, frames: int, layout: int = FrameMajor):
+        _check(out, torch.int32, "out")
+        if out.numel() != frames * self.n_lanes * 2:
+            raise ValueError("out.len() != frames * lanes * 2")
+        call("sweep_i32", C.c_void_p(self.state.data_ptr()), C.c_void_p(out.data_ptr()), self.n_lanes, frames, layout,
+             _stream_ptr(out))
+        return out
+
+    def emitted(self) -> torch.Tensor:
+        """samples each lane has produced since the state was created (i64; where a lane that ended stopped)"""
+        return _i64_of(self.state[5], self.state[6])
 
 
 class FmDisc(_LaneOp):

@@ -889,6 +889,52 @@ double idsp_cordic_circular_gain(void);
 double idsp_cordic_hyperbolic_gain(void);
 
 /* ------------------------------------------------------------------------ */
+/* exponential swept sine: `Sweep`, `AccuOsc` (src/sweptsine.rs)            */
+/* ------------------------------------------------------------------------ */
+/*
+ * Per lane `AccuOsc<Sweep>` with `Osc` for `W<i32>` (src/sweptsine.rs:22-32, :180-188): an exponentially growing phase increment
+ * `state: i64` with a first-order delta-sigma modulator in its low word, integrated by `Integrator<Wrapping<i64>>`
+ * (dsp-process/src/basic.rs:461-466) into `accu`, whose high word is the argument of cossin.  One frame:
+ *     s  = state
+ *     t  = wrapping_i64(s + 2^31) >> 32           arithmetic shift; t fits an i32
+ *     ns = s + rate * t                           exact; rate * t fits an i64
+ *     if ns is outside i64:                       the reference's `checked_add` -> None
+ *         out = (0, 0); nothing changes           the lane has ENDED and stays ended
+ *     else:
+ *         state = ns; accu = wrapping_i64(accu + s); emitted += 1
+ *         out = cossin((accu >> 32) as i32)       (re, im) = (cos, sin)
+ * `s + BIAS` is a plain `+` in the reference: it wraps in a release build and panics in a debug build; this is the wrapping form.
+ * The reference's iterator stops at the end, a block call has a fixed frame count: an ended lane writes (0, 0) — a pair cossin
+ * never returns — and its state does not move.  "Ended" is a pure function of (state, rate); no flag is stored.
+ * State words per lane: { state lo, state hi, accu lo, accu hi, rate, emitted lo, emitted hi }.  `emitted` counts the samples
+ * produced since the state was created (it wraps): the caller sets it to 0 and reads where each lane stopped from it.
+ * Output element = Complex<i32> = [re, im] adjacent, laid out as in idsp_dds_i32; both layouts, any lane and frame count.
+ */
+#define IDSP_SWEEP_STATE_WORDS 7
+size_t idsp_sweep_state_words(void);
+int idsp_sweep_i32(void *state, int32_t *out, size_t lanes, size_t frames, int layout, void *stream);
+
+/* `Sweep`'s host functions with the reference's types and order of operations.  Host code, no GPU needed.
+ * idsp_sweep_fit: `Sweep::fit(stop, harmonics, cycles)` (:108-118) in f32 — stop: the highest frequency in units of the sample
+ * rate (0 ..= 0.5), harmonics: how many harmonics the sweep covers, cycles: phase wraps per harmonic (>= 1).  `cycles as i64`
+ * truncates, the `<< 32` drops bits.  IDSP_EINVAL with idsp_last_error() = "Stop out of bounds" (a NaN stop included) or
+ * "Start out of bounds" (state <= 0), the reference's `SweepError` texts; rate and state are written on success only.
+ * The descriptors (:43-81) are f64: rate() = ln_1p(rate / 2^32), delay(h) = ln(h) / rate(), octave() = LN_2 / rate(),
+ * decade() = LN_10 / rate(), cycles() = state / (2^32 rate), state() = cycles() rate(), continuous(t) = cycles() exp(rate() t).
+ * idsp_sweep_inverse_filter: `Sweep::inverse_filter(f)` (:93-101) in f32, out = [re, im].
+ * The f32 arguments travel as double and are narrowed to f32 on entry, as in idsp_pll_from_zpk (every f32 is a double).
+ * `Osc` for f32 and f64 (libm `sin_cos` of radians) has no entry: it cannot be held to bit equality on the device. */
+int idsp_sweep_fit(double stop, double harmonics, double cycles, int32_t *rate, int64_t *state);
+double idsp_sweep_rate(int32_t rate);
+double idsp_sweep_delay(int32_t rate, double harmonic);
+double idsp_sweep_octave(int32_t rate);
+double idsp_sweep_decade(int32_t rate);
+double idsp_sweep_cycles(int32_t rate, int64_t state);
+double idsp_sweep_state(int32_t rate, int64_t state);
+double idsp_sweep_continuous(int32_t rate, int64_t state, double t);
+int idsp_sweep_inverse_filter(int32_t rate, int64_t state, double f, float out[2]);
+
+/* ------------------------------------------------------------------------ */
 /* lane split over several devices in ONE process: idsp_multi_*             */
 /* ------------------------------------------------------------------------ */
 /*

@@ -999,6 +999,71 @@ private:
     DeviceBuffer<uint32_t> state_;
 };
 
+// ------------------------------------------------------- exponential swept sine
+/// `Sweep { rate, state }` (src/sweptsine.rs:12-119).  `fit` and the descriptors are host calls into the library (f32 / f64 with
+/// the reference's order of operations); no GPU needed.
+struct Sweep {
+    int32_t rate = 0;
+    int64_t state = 0;
+    Sweep() = default;
+    Sweep(int32_t rate_, int64_t state_) : rate(rate_), state(state_) {}
+    /// `Sweep::fit(stop, harmonics, cycles)` (:108-118); `SweepError` -> Error(IDSP_EINVAL, "... Stop / Start out of bounds")
+    static Sweep fit(float stop, float harmonics, float cycles)
+    {
+        Sweep s;
+        check(idsp_sweep_fit(stop, harmonics, cycles, &s.rate, &s.state));
+        return s;
+    }
+    double rate_f() const { return idsp_sweep_rate(rate); }                       ///< `rate()` (:43-45)
+    double delay(double harmonic) const { return idsp_sweep_delay(rate, harmonic); }
+    double octave() const { return idsp_sweep_octave(rate); }
+    double decade() const { return idsp_sweep_decade(rate); }
+    double cycles() const { return idsp_sweep_cycles(rate, state); }
+    double state_f() const { return idsp_sweep_state(rate, state); }              ///< `state()` (:67-69)
+    double continuous(double t) const { return idsp_sweep_continuous(rate, state, t); }
+    std::array<float, 2> inverse_filter(float f) const                            ///< [re, im] (:93-101)
+    {
+        std::array<float, 2> out{};
+        check(idsp_sweep_inverse_filter(rate, state, f, out.data()));
+        return out;
+    }
+};
+
+/// Per-lane `AccuOsc<Sweep>` (src/sweptsine.rs:160-188) with `Osc` for `W<i32>`.  A lane whose sweep has ended writes (0, 0).
+class SweepOsc {
+public:
+    explicit SweepOsc(const std::vector<Sweep> &sweeps, void *stream = nullptr) : lanes_(sweeps.size()), stream_(stream)
+    {
+        std::vector<uint32_t> st(IDSP_SWEEP_STATE_WORDS * lanes_, 0u);  // accu = 0, emitted = 0
+        for (size_t l = 0; l < lanes_; l++) {
+            st[l] = uint32_t(uint64_t(sweeps[l].state)), st[lanes_ + l] = uint32_t(uint64_t(sweeps[l].state) >> 32);
+            st[4 * lanes_ + l] = uint32_t(sweeps[l].rate);
+        }
+        state_ = DeviceBuffer<uint32_t>(st);
+    }
+    DeviceBuffer<uint32_t> &state() { return state_; }
+    /// out: `Complex<i32>` = [re, im] per sample (build the view with width 2)
+    template <class Layout>
+    void generate(ViewMut<int32_t, Layout> out)
+    {
+        require(out.lanes == lanes_, "view shape mismatch");
+        check(idsp_sweep_i32(state_.data(), out.flat, lanes_, out.frames, Layout::value, stream_));
+    }
+    /// samples each lane has produced (where a lane that ended stopped); synchronises
+    std::vector<uint64_t> emitted() const
+    {
+        const std::vector<uint32_t> st = state_.to_host();
+        std::vector<uint64_t> e(lanes_);
+        for (size_t l = 0; l < lanes_; l++) e[l] = uint64_t(st[5 * lanes_ + l]) | (uint64_t(st[6 * lanes_ + l]) << 32);
+        return e;
+    }
+
+private:
+    size_t lanes_;
+    void *stream_;
+    DeviceBuffer<uint32_t> state_;
+};
+
 // ------------------------------------------------------- phase consumers
 /// `Wrap` (src/unwrap.rs:15-27)
 enum class Wrap : int8_t { Negative = -1, None = 0, Positive = 1 };

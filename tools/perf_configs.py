@@ -453,6 +453,63 @@ def cordic(n, iters, tag):
                    times_copy=round(med / cm, 3), atan2_ms_median=round(am, 4), times_atan2=round(med / am, 3), dispatch=call("last_kernel").decode())
 
 
+def sweep(lanes, frames, layout, iters, tag, repeats=3):
+    """The swept sine at one shape: idsp_sweep_i32 beside idsp_dds_i32 on the same output buffer, and for every (order, cascade)
+    the swept lock-in as the library offers it — idsp_sweep_i32 into an LO buffer + idsp_lockin_i32_lo_process, timed together,
+    28 bytes per sample — beside idsp_lockin_i32_process (the `Accu` LO: 12 bytes per sample).  (A fused entry on the
+    one-thread-per-lane stream kernels was timed with these lines and dropped: profiles/NOTES.md, profiles/sweep_perf.jsonl.)
+    Every line is timed `repeats` times in turn, so that the spread of a kernel's own runs stands beside the differences.  The
+    sweeps are `fit(0.5, 1e6, 1.0)` with random accumulators: they live for 2.7e7 frames, far beyond what is timed here (an ended
+    lane runs the same instructions anyway)."""
+    lm = "LM" if layout else "FM"
+    rate, state = C.c_int32(), C.c_int64()
+    call("sweep_fit", 0.5, 1e6, 1.0, C.byref(rate), C.byref(state))
+
+    def sweep_words(st):
+        st[0], st[1], st[4] = state.value & 0xFFFFFFFF, state.value >> 32, rate.value
+        st[2] = torch.randint(-(1 << 31), (1 << 31) - 1, (lanes,), dtype=torch.int64, device=dev).to(torch.int32)
+        st[3] = torch.randint(-(1 << 31), (1 << 31) - 1, (lanes,), dtype=torch.int64, device=dev).to(torch.int32)
+
+    n = lanes * frames
+    y = torch.empty(n * 2, dtype=torch.int32, device=dev)
+    sst = torch.zeros((_abi.SWEEP_STATE_WORDS, lanes), dtype=torch.int32, device=dev)
+    sweep_words(sst)
+    dst = torch.zeros((2, lanes), dtype=torch.int32, device=dev)
+    dst[1] = torch.randint(-(1 << 31), (1 << 31) - 1, (lanes,), dtype=torch.int64, device=dev).to(torch.int32)
+    for r in range(repeats):
+        med, mn = timeit(lambda: call("dds_i32", p(dst), p(y), lanes, frames, layout, sptr()), iters)
+        report(f"{tag}:dds {lm} {lanes}x{frames}", n, "sample", 8 * n, med, mn, repeat=r)
+        med, mn = timeit(lambda: call("sweep_i32", p(sst), p(y), lanes, frames, layout, sptr()), iters)
+        report(f"{tag}:sweep {lm} {lanes}x{frames}", n, "sample", 8 * n, med, mn, repeat=r)
+    x = torch.randint(-(1 << 28), 1 << 28, (n,), dtype=torch.int32, device=dev)
+    lo = torch.empty(n * 2, dtype=torch.int32, device=dev)
+    k = math.pi * (1 << 31) * 1e-3  # f0 = 1e-3 fn (src/lowpass.rs:31-38), as in lockin()
+    for order in (1, 2):
+        for cascade in (1, 2, 3, 4):
+            cfg = _abi.LockinI32()
+            cfg.order, cfg.cascade = order, cascade
+            for c in range(cascade):
+                if order == 1:
+                    cfg.k[c][0] = int(k)
+                else:
+                    cfg.k[c][0], cfg.k[c][1] = int(k * k / (1 << 32)), -int(k * math.sqrt(2.0))
+            arm_words = call("lockin_state_words", C.byref(cfg)) - 2
+            ast = torch.zeros((arm_words, lanes), dtype=torch.int32, device=dev)
+            pst = torch.zeros((2 + arm_words, lanes), dtype=torch.int32, device=dev)
+            pst[1] = dst[1]
+
+            def chain():
+                call("sweep_i32", p(sst), p(lo), lanes, frames, layout, sptr())
+                call("lockin_i32_lo_process", C.byref(cfg), p(ast), p(x), p(lo), p(y), lanes, frames, layout, sptr())
+
+            name = f"Lowpass<{order}>x{cascade} {lm} {lanes}x{frames}"
+            for r in range(repeats):
+                med, mn = timeit(chain, iters)
+                report(f"{tag}:sweep + lockin_lo {name}", n, "sample", 28 * n, med, mn, repeat=r)
+                med, mn = timeit(lambda: call("lockin_i32_process", C.byref(cfg), p(pst), p(x), p(y), lanes, frames, layout, sptr()), iters)
+                report(f"{tag}:lockin {name}", n, "sample", 12 * n, med, mn, repeat=r)
+
+
 def copy_ref(nbytes, iters):
     a = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     b = torch.empty_like(a)
@@ -622,6 +679,11 @@ def main():
                 pfb(8, 1, 16384, 4096, layout, it, "pfb", inplace)
         pfb(8, 1, 64, 1 << 20, FM, it, "pfb")
         pfb(8, 1, 64, 1 << 20, LM, it, "pfb")
+    # the swept sine at 65536 and 16384 lanes x 4096 in both layouts (`sweep`), or one shape per process: sweep_65536_fm, ...
+    for lanes in (65536, 16384):
+        for layout in (FM, LM):
+            if want("sweep") or (sel is not None and f"sweep_{lanes}_{'lm' if layout else 'fm'}" in sel):
+                sweep(lanes, 4096, layout, it, "sweep")
     if want("cordic"):  # the CORDIC family at 2^26 elements with and without z, beside a copy of the same bytes and atan2 at the same n
         cordic(1 << 26, it, "cordic")
     if want("lockinc"):  # `Lockin<C>` with biquad arms at the C4 shape (thread-per-lane stream kernels)
