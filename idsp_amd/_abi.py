@@ -361,6 +361,28 @@ SWEEP = {
 }
 UTILS.update(SWEEP)
 
+# reciprocal PLL and the batch LO its `Accu` drives (product only, no twin in the checker library: parity rests on
+# tests/_rpll_spec.py); merged into UTILS the way PHASE and SWEEP are
+RPLL_STATE_WORDS = 4  # IDSP_RPLL_STATE_WORDS: x, ff, f, y
+
+
+class Rpll(C.Structure):
+    """idsp_rpll: `RPLLConfig` (src/rpll.rs:23-36)"""
+    _fields_ = [("dt2", C.c_int32), ("shift_frequency", C.c_int32), ("shift_phase", C.c_int32)]
+
+
+class AccuLo(C.Structure):
+    """idsp_accu_lo: 2^batch_log2 samples per update, `Accu * harmonic + Accu::new(offset, 0)`"""
+    _fields_ = [("batch_log2", C.c_int32), ("harmonic", C.c_int32), ("offset", C.c_int32)]
+
+
+RPLL = {
+    "rpll_state_words": (_SZ, []),
+    "rpll_i32": (_I, [_P, _P, _P, _P, _SZ, _SZ, _I, _P]),  # cfg, state, ts, accu, lanes, frames, layout, stream
+    "accu_lo_i32": (_I, [_P, _P, _P, _SZ, _SZ, _I, _P]),   # cfg, accu, lo, lanes, updates, layout, stream
+}
+UTILS.update(RPLL)
+
 SHARD_FN = C.CFUNCTYPE(_I, _P, _I, _SZ, _SZ, _P)  # idsp_shard_fn
 
 

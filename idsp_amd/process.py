@@ -26,6 +26,7 @@ own:
     PolyphaseBank (* Dft4), prototype()  (examples/polyphase_channelizer.rs) PolyphaseBank.prototype(taps).lanes(N)
     overflowing_sub / saturating_scale   (unwrap.rs:73-101) overflowing_sub(y, x), saturating_scale(lo, hi, shift)
     Sweep / AccuOsc<Sweep>               (sweptsine.rs:12-188) Sweep.fit(stop, harmonics, cycles), SweepOsc(N, rate, state)
+    RPLLConfig / RPLL, the returned Accu (rpll.rs:13-90, accu.rs:34-54) RPLLConfig(dt2, sf, sp).lanes(N), accu_lo(accu, lo, ...)
     cossin(phase)                        (cossin.rs:14)  cossin(phases)
     atan2(y, x) / Complex::arg           (atan2.rs:66)   atan2(xy)
     cordic::{cos_sin, sqrt_atan2, ...}   (cordic.rs:80-107) cordic_cos_sin(xy, z), cordic_sqrt_atan2(xy, z), ...
@@ -50,7 +51,7 @@ __all__ = [
     "FrameMajor", "LaneMajor", "View", "ViewMut", "Biquad", "BiquadClamp", "Cascade",
     "DirectForm1", "DirectForm2Transposed", "DirectForm1Wide", "DirectForm1Dither", "DirectForm",
     "Split", "Lanes", "ByLane", "HbfDecCascade", "HbfIntCascade", "FirSym", "Cic", "Normal", "Wdf", "HBF_TAPS", "HBF_TAPS_98",
-    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "Sweep", "SweepOsc", "FmDisc", "PLL", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
+    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "Sweep", "SweepOsc", "FmDisc", "PLL", "RPLLConfig", "RPLLLanes", "accu_lo", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
     "cordic_circular_gain", "cordic_hyperbolic_gain", "sos", "sos_clamp_wide", "IdspError",
 ]
 
@@ -1054,6 +1055,76 @@ class PLLLanes(_LaneOp):
     def frequency(self) -> torch.Tensor:
         """`PLLState::frequency()` of every lane (src/pll.rs:84-86), int32."""
         return self.state[7].clone()
+
+
+class RPLLConfig:
+    """`RPLLConfig { dt2, shift_frequency, shift_phase }` (src/rpll.rs:23-36), validated as idsp_rpll_i32 validates it: the ranges in
+    which every shift of `process` (:58-74) is defined.  `.lanes(n)` gives the per-lane `RPLL` states."""
+
+    def __init__(self, dt2: int, shift_frequency: int, shift_phase: int):
+        dt2, sf, sp = int(dt2), int(shift_frequency), int(shift_phase)
+        if not 0 <= dt2 <= 30:
+            raise ValueError("dt2 must be in 0..=30")
+        if not dt2 < sf <= 32:
+            raise ValueError("shift_frequency must be in dt2 + 1..=32 (`1u32 << (32 + dt2 - shift_frequency)`, src/rpll.rs:64)")
+        if not dt2 <= sp <= dt2 + 31:
+            raise ValueError("shift_phase must be in dt2..=dt2 + 31")
+        self.dt2, self.shift_frequency, self.shift_phase = dt2, sf, sp
+
+    def lanes(self, n: int, device="cuda") -> "RPLLLanes":
+        return RPLLLanes(self, n, device)
+
+
+class RPLLLanes:
+    """`RPLLConfig::process` per lane (src/rpll.rs:47-77) on zeroed `RPLL` states (`RPLL::default()`): timestamps
+    `ts[..., 2] = {some, x}` in, the returned `Accu` `accu[..., 2] = {state, step}` out; ts and accu are separate tensors."""
+
+    def __init__(self, cfg: RPLLConfig, n_lanes: int, device="cuda"):
+        load()
+        self.cfg = _abi.Rpll(cfg.dt2, cfg.shift_frequency, cfg.shift_phase)
+        self.n_lanes, self.device = int(n_lanes), torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("idsp_amd runs on the GPU only")
+        self.state = torch.zeros((_abi.RPLL_STATE_WORDS, self.n_lanes), dtype=torch.int32, device=self.device)
+
+    def process(self, ts: torch.Tensor, accu: torch.Tensor, frames: int, layout: int = FrameMajor) -> torch.Tensor:
+        _check(ts, torch.int32, "ts")
+        _check(accu, torch.int32, "accu")
+        if ts.device != self.state.device or accu.device != self.state.device:
+            raise ValueError("ts and accu must be on the device of the state")
+        if layout not in (FrameMajor, LaneMajor) or int(frames) < 0:
+            raise ValueError("layout must be FrameMajor or LaneMajor, frames >= 0")
+        if ts.numel() != frames * self.n_lanes * 2 or accu.numel() != ts.numel():
+            raise ValueError("ts.len() and accu.len() must be frames * lanes * 2")
+        call("rpll_i32", C.byref(self.cfg), C.c_void_p(self.state.data_ptr()), C.c_void_p(ts.data_ptr()), C.c_void_p(accu.data_ptr()),
+             self.n_lanes, frames, layout, _stream_ptr(ts))
+        return accu
+
+    def phase(self) -> torch.Tensor:
+        """`RPLL::phase()` of every lane (src/rpll.rs:82-84), int32."""
+        return self.state[3].clone()
+
+    def frequency(self) -> torch.Tensor:
+        """`RPLL::frequency()` of every lane (src/rpll.rs:87-89): the u32 bits as int32."""
+        return self.state[2].clone()
+
+
+def accu_lo(accu: torch.Tensor, lo: torch.Tensor, n_lanes: int, updates: int, batch_log2: int, harmonic: int = 1, offset: int = 0,
+            layout: int = FrameMajor) -> torch.Tensor:
+    """The LO of `updates` batches of `2^batch_log2` samples from the `Accu`s an RPLL returned (idsp_accu_lo_i32):
+    `Accu::new(state, step >> batch_log2) * harmonic + Accu::new(offset, 0)` iterated by `next()` into `Complex::from_angle`.
+    `lo[..., 2] = {re, im}` is what `LockinLo.process` takes."""
+    if not 0 <= int(batch_log2) <= 24:
+        raise ValueError("batch_log2 must be in 0..=24")
+    _check(accu, torch.int32, "accu")
+    _check(lo, torch.int32, "lo")
+    if accu.device != lo.device:
+        raise ValueError("accu and lo must be on one device")
+    if accu.numel() != updates * n_lanes * 2 or lo.numel() != (updates << batch_log2) * n_lanes * 2:
+        raise ValueError("accu.len() must be updates * lanes * 2 and lo.len() (updates << batch_log2) * lanes * 2")
+    cfg = _abi.AccuLo(int(batch_log2), _i32(harmonic), _i32(offset))
+    call("accu_lo_i32", C.byref(cfg), C.c_void_p(accu.data_ptr()), C.c_void_p(lo.data_ptr()), n_lanes, updates, layout, _stream_ptr(lo))
+    return lo
 
 
 class Unwrapper:

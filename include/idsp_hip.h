@@ -935,6 +935,72 @@ double idsp_sweep_continuous(int32_t rate, int64_t state, double t);
 int idsp_sweep_inverse_filter(int32_t rate, int64_t state, double f, float out[2]);
 
 /* ------------------------------------------------------------------------ */
+/* reciprocal PLL: `RPLLConfig`, `RPLL` (src/rpll.rs) and the batch LO       */
+/* ------------------------------------------------------------------------ */
+/*
+ * Per lane `RPLLConfig::process` on `RPLL` (src/rpll.rs:13-78): quantised edge timestamps of a reference signal, at most one per
+ * `update()`, in; the phase and frequency of the `update()` calls relative to that reference (2^32 = one turn, one turn per
+ * update) out, as the `Accu<W<i32>>` the reference returns.  One independent recurrence per lane, all integer and bit-exact.
+ *   ts   one `Option<W<i32>>` per lane and frame as two adjacent words: ts[index(f,l)*2 + {0: some, 1: x}].  some == 0 is `None`
+ *        and x is then ignored; any other value is `Some(x)`.
+ *   accu the returned `Accu` as two adjacent words: accu[index(f,l)*2 + {0: state = y, 1: step = f as i32}] (:76).
+ * index(f,l) as everywhere: FRAME_MAJOR f*lanes + l, LANE_MAJOR l*frames + f; any lane count.  ts and accu are separate buffers
+ * (any overlap is IDSP_EINVAL, there is no in-place form) and 8-byte aligned.
+ * One sample, with the wrapping semantics of a release build (:47-77):
+ *     y += (i32)f                                              :51
+ *     if some:
+ *         dx    = x - x0 (wrapping i32);  x0 = x               :54-56
+ *         p64   = (u64)ff * (u64)(i64)dx                       :58   `dx.0 as u64` SIGN-extends; the product wraps mod 2^64
+ *         p_sig = (u32)((p64 + (1 << (sf-1))) >> sf)           :60-62 u64 wrapping add, logical shift, truncation
+ *         p_ref = 1u32 << (32 + dt2 - sf)                      :64
+ *         ff   += p_ref - p_sig            (wrapping u32)      :66
+ *         dt    = (u32)((-x) & ((1 << dt2) - 1))               :68
+ *         y_ref = (i32)((f >> dt2) * dt)                       :70   the OLD f, logical shift, wrapping u32 product
+ *         dy    = (y_ref - y) >> (sp - dt2)                    :72   y already advanced; wrapping sub, ARITHMETIC shift
+ *         f     = ff + (u32)dy                                 :74   the NEW ff
+ *     return { y, (i32)f }
+ * with sf = shift_frequency, sp = shift_phase.  State words per lane (`RPLL`, :13-18), state[w*lanes + lane]: { x, ff, f, y }; all
+ * zero is `RPLL::default()`.  Read at entry and written at exit: consecutive calls on one state equal one long call bit for bit.
+ * `phase()` / `frequency()` (:80-90) after a call are state word 3 / state word 2.
+ * IDSP_EINVAL unless 0 <= dt2 <= 30, dt2 < shift_frequency <= 32 and dt2 <= shift_phase <= dt2 + 31: the ranges in which every
+ * shift above is defined.  They come from the shifts, not from the reference's `debug_assert`s (:48-49):
+ * shift_frequency == dt2 passes the assert, but `1u32 << 32` at :64 then overflows (a panic in a debug build, a shift by 0 in
+ * a release build), so it is rejected.
+ */
+typedef struct idsp_rpll {
+    int32_t dt2;              /* 1 << dt2: counter rate to update() rate ratio (:24-25) */
+    int32_t shift_frequency;  /* 1 << shift_frequency: frequency lock settling time in counter periods (:26-31) */
+    int32_t shift_phase;      /* phase lock settling time, usually shift_frequency - 1 (:32-35) */
+} idsp_rpll;                  /* RPLLConfig, src/rpll.rs:23-36 */
+#define IDSP_RPLL_STATE_WORDS 4
+size_t idsp_rpll_state_words(void);
+int idsp_rpll_i32(const idsp_rpll *cfg, void *state, const int32_t *ts, int32_t *accu, size_t lanes, size_t frames, int layout,
+                  void *stream);
+
+/* The local oscillator of a batch from the `Accu` the RPLL returned.  `update()` runs once per batch of 2^k samples
+ * (k = batch_log2), and the sample phases of the batch are iterated from the returned `Accu` with the reference's own operators:
+ * `Accu * T` (src/accu.rs:40-46), `Accu + Accu` (:48-54), the pre-incrementing `next()` (:34-37) and
+ * `Complex::<i32>::from_angle` (src/complex.rs:237-240, i.e. cossin).  accu: `updates` rows of { state, step } pairs in the layout
+ * of idsp_rpll_i32's output with frames = updates.  lo: `Complex<i32>` [re, im] for frames = updates << k samples per lane in the
+ * same layout — exactly the `lo` argument of idsp_lockin_i32_lo_process.  For sample t = u*2^k + j, 0 <= j < 2^k, of lane l, with
+ * a = accu[u, l]:
+ *     sample = Accu::new(a.state, ((u32)a.step >> k) as i32) * harmonic + Accu::new(offset, 0)     all wrapping
+ *     phase  = sample.state + (j + 1) * sample.step                                                j + 1 calls of next()
+ *     lo[t, l] = cossin(phase)                                                                      re = cos, im = sin
+ * The LOGICAL shift of the step by k is the one operation here that is not in the reference: the RPLL's f is phase per
+ * update(), and a batch holds 2^k samples per update.
+ * No state: a call on rows [u0, u1) equals those rows of a longer call.  IDSP_EINVAL unless 0 <= batch_log2 <= 24 and
+ * updates << batch_log2 is a frame count every stream entry accepts (<= 2^40); accu and lo are 8-byte aligned and must not overlap.
+ */
+typedef struct idsp_accu_lo {
+    int32_t batch_log2;  /* k: 2^k samples per update() */
+    int32_t harmonic;    /* `Accu * harmonic` */
+    int32_t offset;      /* `+ Accu::new(offset, 0)`: phase offset of the LO */
+} idsp_accu_lo;
+int idsp_accu_lo_i32(const idsp_accu_lo *cfg, const int32_t *accu, int32_t *lo, size_t lanes, size_t updates, int layout,
+                     void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* lane split over several devices in ONE process: idsp_multi_*             */
 /* ------------------------------------------------------------------------ */
 /*

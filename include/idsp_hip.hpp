@@ -1266,4 +1266,74 @@ private:
     DeviceBuffer<uint32_t> state_;
 };
 
+// ------------------------------------------------------- reciprocal PLL
+class RPLLLanes;
+/// `RPLLConfig { dt2, shift_frequency, shift_phase }` (src/rpll.rs:23-36), validated as idsp_rpll_i32 validates it: the ranges in
+/// which every shift of `process` (:58-74) is defined (shift_frequency == dt2 would be `1u32 << 32` at :64).
+struct RPLLConfig {
+    int32_t dt2, shift_frequency, shift_phase;
+    RPLLConfig(int32_t dt2_, int32_t shift_frequency_, int32_t shift_phase_) : dt2(dt2_), shift_frequency(shift_frequency_), shift_phase(shift_phase_)
+    {
+        require(dt2 >= 0 && dt2 <= 30, "dt2 must be in 0..=30");
+        require(shift_frequency > dt2 && shift_frequency <= 32, "shift_frequency must be in dt2 + 1..=32");
+        require(shift_phase >= dt2 && shift_phase <= dt2 + 31, "shift_phase must be in dt2..=dt2 + 31");
+    }
+    inline RPLLLanes lanes(size_t n, void *stream = nullptr) const;
+};
+
+/// `RPLLConfig::process` per lane (src/rpll.rs:47-77): zero state = `RPLL::default()`.
+class RPLLLanes {
+public:
+    RPLLLanes(const RPLLConfig &cfg, size_t lanes, void *stream = nullptr)
+        : cfg_{cfg.dt2, cfg.shift_frequency, cfg.shift_phase}, lanes_(lanes), stream_(stream), state_(idsp_rpll_state_words() * lanes)
+    {
+    }
+    DeviceBuffer<uint32_t> &state() { return state_; }
+    /// ts: `Option<W<i32>>` = {some, x} per sample, accu: the returned `Accu` = {state, step} (build both views with width 2); separate buffers
+    template <class Layout>
+    void process_view(View<int32_t, Layout> ts, ViewMut<int32_t, Layout> accu)
+    {
+        require(ts.frames == accu.frames && ts.lanes == lanes_ && accu.lanes == lanes_, "view shape mismatch");
+        check(idsp_rpll_i32(&cfg_, state_.data(), ts.flat, accu.flat, lanes_, ts.frames, Layout::value, stream_));
+    }
+    /// `RPLL::phase()` / `RPLL::frequency()` of every lane (src/rpll.rs:80-90); synchronises
+    std::vector<int32_t> phase() const
+    {
+        const std::vector<uint32_t> w = word(3);
+        return std::vector<int32_t>(w.begin(), w.end());
+    }
+    std::vector<uint32_t> frequency() const { return word(2); }
+
+private:
+    std::vector<uint32_t> word(size_t w) const
+    {
+        if (lanes_) check(idsp_stream_sync(stream_));  // no lanes: nothing was launched, and no device is needed
+        const std::vector<uint32_t> st = state_.to_host();
+        return std::vector<uint32_t>(st.begin() + w * lanes_, st.begin() + (w + 1) * lanes_);
+    }
+    idsp_rpll cfg_;
+    size_t lanes_;
+    void *stream_;
+    DeviceBuffer<uint32_t> state_;
+};
+inline RPLLLanes RPLLConfig::lanes(size_t n, void *stream) const { return RPLLLanes(*this, n, stream); }
+
+/// The LO of a batch from the `Accu`s an RPLL returned (idsp_accu_lo_i32): `Accu::new(state, step >> batch_log2) * harmonic +
+/// Accu::new(offset, 0)` iterated by `next()` into `Complex::from_angle`.  accu: `updates` rows of {state, step}, lo:
+/// `updates << batch_log2` rows of [re, im] (both views with width 2) — the `lo` of LockinLo.
+struct AccuLo {
+    int32_t batch_log2, harmonic, offset;
+    explicit AccuLo(int32_t batch_log2_, int32_t harmonic_ = 1, int32_t offset_ = 0) : batch_log2(batch_log2_), harmonic(harmonic_), offset(offset_)
+    {
+        require(batch_log2 >= 0 && batch_log2 <= 24, "batch_log2 must be in 0..=24");
+    }
+    template <class Layout>
+    void process_view(View<int32_t, Layout> accu, ViewMut<int32_t, Layout> lo, void *stream = nullptr) const
+    {
+        require(lo.lanes == accu.lanes && lo.frames == accu.frames << batch_log2, "view shape mismatch");
+        const idsp_accu_lo cfg{batch_log2, harmonic, offset};
+        check(idsp_accu_lo_i32(&cfg, accu.flat, lo.flat, accu.lanes, accu.frames, Layout::value, stream));
+    }
+};
+
 }  // namespace idsp_hip

@@ -510,6 +510,88 @@ def sweep(lanes, frames, layout, iters, tag, repeats=3):
                 report(f"{tag}:lockin {name}", n, "sample", 12 * n, med, mn, repeat=r)
 
 
+def rpll(lanes, frames, layout, iters, tag, chain_too=False, repeats=2):
+    """The reciprocal PLL and the batch LO at one shape.  idsp_rpll_i32 (8 bytes in, 8 out per sample; timestamps of a reference
+    of period 333 +- per lane at dt2 = 8, as the reference's harness makes them) beside idsp_pll_i32 with IDSP_PLL_BOTH (4 in,
+    8 out): compare as a fraction of each one's own bytes.  idsp_accu_lo_i32 for k = 0, 3, 8 at `frames` OUTPUT frames beside
+    idsp_dds_i32 on the same output buffer (the same bytes written; accu_lo also reads 8 / 2^k bytes per sample).  (The lines
+    tagged `accu_lo[circle]` in profiles/rpll_perf.jsonl are a full-circle-table form that was built beside the shipped one, timed
+    with this function and taken out.)
+    chain_too: idsp_rpll_i32 -> idsp_accu_lo_i32 (k = 3) -> idsp_lockin_i32_lo_process timed together beside
+    idsp_lockin_i32_process (internal phase) at the same output shape."""
+    lm = "LM" if layout else "FM"
+    n = lanes * frames
+    form = "table512"
+
+    def timestamps(updates):
+        period = torch.randint(300, 500, (lanes,), dtype=torch.int64, device=dev)
+        t = torch.arange(updates, dtype=torch.int64, device=dev) * 256
+        tt, pp = (t[:, None], period[None, :]) if layout == 0 else (t[None, :], period[:, None])
+        edge = (tt // pp) * pp  # the last edge at or before `time`; due when it is younger than one update
+        ts = torch.stack([(tt - edge < 256).to(torch.int32), edge.to(torch.int32)], dim=-1).reshape(-1).contiguous()
+        return ts
+
+    cfg = _abi.Rpll(8, 9, 8)
+    ts = timestamps(frames)
+    accu = torch.empty(n * 2, dtype=torch.int32, device=dev)
+    rst = torch.zeros((_abi.RPLL_STATE_WORDS, lanes), dtype=torch.int32, device=dev)
+    x = (ts[1::2].contiguous() << 8)  # any i32 phase stream of the same shape for the PLL
+    pst = torch.zeros((_abi.PLL_STATE_WORDS, lanes), dtype=torch.int32, device=dev)
+    ba = (C.c_int32 * 3)()
+    call("pll_from_bandwidth", 1e-2, 4.0, ba)
+    for r in range(repeats):
+        med, mn = timeit(lambda: call("rpll_i32", C.byref(cfg), p(rst), p(ts), p(accu), lanes, frames, layout, sptr()), iters)
+        report(f"{tag}:rpll {lm} {lanes}x{frames}", n, "sample", 16 * n, med, mn, repeat=r, dispatch=call("last_kernel").decode())
+        med, mn = timeit(lambda: call("pll_i32", ba, p(pst), p(x), p(accu), lanes, frames, layout, _abi.PLL_BOTH, sptr()), iters)
+        report(f"{tag}:pll_both {lm} {lanes}x{frames}", n, "sample", 12 * n, med, mn, repeat=r, dispatch=call("last_kernel").decode())
+    del ts, x
+    lo = torch.empty(n * 2, dtype=torch.int32, device=dev)
+    dst = torch.zeros((2, lanes), dtype=torch.int32, device=dev)
+    dst[1] = torch.randint(-(1 << 31), (1 << 31) - 1, (lanes,), dtype=torch.int64, device=dev).to(torch.int32)
+    for k in (0, 3, 8):
+        updates = frames >> k
+        a = torch.randint(-(1 << 31), (1 << 31) - 1, (updates * lanes * 2,), dtype=torch.int64, device=dev).to(torch.int32)
+        lc = _abi.AccuLo(k, 1, 0)
+        for r in range(repeats):
+            med, mn = timeit(lambda: call("accu_lo_i32", C.byref(lc), p(a), p(lo), lanes, updates, layout, sptr()), iters)
+            report(f"{tag}:accu_lo[{form}] k={k} {lm} {lanes}x{frames}", n, "sample", 8 * n + 8 * updates * lanes, med, mn, repeat=r, dispatch=call("last_kernel").decode())
+            med, mn = timeit(lambda: call("dds_i32", p(dst), p(lo), lanes, frames, layout, sptr()), iters)
+            report(f"{tag}:dds {lm} {lanes}x{frames}", n, "sample", 8 * n, med, mn, repeat=r, dispatch=call("last_kernel").decode())
+        del a
+    if not chain_too:
+        return
+    k, updates = 3, frames >> 3
+    ts = timestamps(updates)
+    lc = _abi.AccuLo(k, 1, 0)
+    xs = torch.randint(-(1 << 28), 1 << 28, (n,), dtype=torch.int32, device=dev)
+    y = torch.empty(n * 2, dtype=torch.int32, device=dev)
+    kk = math.pi * (1 << 31) * 1e-3
+    for order, cascade in ((1, 1), (2, 1), (2, 2)):
+        lcfg = _abi.LockinI32()
+        lcfg.order, lcfg.cascade = order, cascade
+        for c in range(cascade):
+            if order == 1:
+                lcfg.k[c][0] = int(kk)
+            else:
+                lcfg.k[c][0], lcfg.k[c][1] = int(kk * kk / (1 << 32)), -int(kk * math.sqrt(2.0))
+        arm_words = call("lockin_state_words", C.byref(lcfg)) - 2
+        ast = torch.zeros((arm_words, lanes), dtype=torch.int32, device=dev)
+        lst = torch.zeros((2 + arm_words, lanes), dtype=torch.int32, device=dev)
+        lst[1] = dst[1]
+
+        def chain():
+            call("rpll_i32", C.byref(cfg), p(rst), p(ts), p(accu), lanes, updates, layout, sptr())
+            call("accu_lo_i32", C.byref(lc), p(accu), p(lo), lanes, updates, layout, sptr())
+            call("lockin_i32_lo_process", C.byref(lcfg), p(ast), p(xs), p(lo), p(y), lanes, frames, layout, sptr())
+
+        name = f"Lowpass<{order}>x{cascade} {lm} {lanes}x{frames}"
+        for r in range(repeats):
+            med, mn = timeit(chain, iters)
+            report(f"{tag}:rpll + accu_lo[{form}] + lockin_lo {name}", n, "sample", 28 * n + 24 * updates * lanes, med, mn, repeat=r)
+            med, mn = timeit(lambda: call("lockin_i32_process", C.byref(lcfg), p(lst), p(xs), p(y), lanes, frames, layout, sptr()), iters)
+            report(f"{tag}:lockin {name}", n, "sample", 12 * n, med, mn, repeat=r)
+
+
 def copy_ref(nbytes, iters):
     a = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     b = torch.empty_like(a)
@@ -684,6 +766,15 @@ def main():
         for layout in (FM, LM):
             if want("sweep") or (sel is not None and f"sweep_{lanes}_{'lm' if layout else 'fm'}" in sel):
                 sweep(lanes, 4096, layout, it, "sweep")
+    # the reciprocal PLL and the batch LO (`rpll`, or one shape per process: rpll_65536_fm, ... rpll_16384_lm; rpll_chain_fm / _lm: the
+    # chain beside the internal-phase lock-in at 32768 x 4096)
+    for lanes in (65536, 16384):
+        for layout in (FM, LM):
+            if want("rpll") or (sel is not None and f"rpll_{lanes}_{'lm' if layout else 'fm'}" in sel):
+                rpll(lanes, 4096, layout, it, "rpll")
+    for layout in (FM, LM):
+        if want("rpll") or (sel is not None and f"rpll_chain_{'lm' if layout else 'fm'}" in sel):
+            rpll(32768, 4096, layout, it, "rpll_chain", chain_too=True)
     if want("cordic"):  # the CORDIC family at 2^26 elements with and without z, beside a copy of the same bytes and atan2 at the same n
         cordic(1 << 26, it, "cordic")
     if want("lockinc"):  # `Lockin<C>` with biquad arms at the C4 shape (thread-per-lane stream kernels)
