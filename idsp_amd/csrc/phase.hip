@@ -34,6 +34,13 @@ int check_phase_args(const void *state, const void *x, const void *y, size_t lan
     return IDSP_OK;
 }
 
+// the two-word output forms (i64 phase, {phase, frequency} pairs) store whole elements: y on the 8-byte grid
+int check_pair_out(const void *y)
+{
+    if (reinterpret_cast<uintptr_t>(y) % 8) return fail(IDSP_EINVAL, "y holds 8-byte elements: it must be 8-byte aligned");
+    return IDSP_OK;
+}
+
 }  // namespace
 }  // namespace idsp
 
@@ -70,6 +77,8 @@ int idsp_pll_i32(const int32_t ba[3], void *state, const int32_t *x, int32_t *y,
     if (output != IDSP_PLL_PHASE && output != IDSP_PLL_FREQUENCY && output != IDSP_PLL_BOTH)
         return fail(IDSP_EINVAL, "output %d is none of IDSP_PLL_PHASE, IDSP_PLL_FREQUENCY, IDSP_PLL_BOTH", output);
     if (int rc = check_phase_args(state, x, y, lanes, frames, layout)) return rc;
+    if (output == IDSP_PLL_BOTH)
+        if (int rc = check_pair_out(y)) return rc;
     if (lanes == 0 || frames == 0) return IDSP_OK;
     const PllParams p{{ba[0], ba[1], ba[2]}};
     if (output == IDSP_PLL_PHASE) return launch_stream<PllProc<0>>(p, state, x, y, lanes, frames, layout, as_stream(stream));
@@ -87,6 +96,7 @@ int idsp_unwrap_i32(void *state, const int32_t *x, int32_t *dx, size_t lanes, si
 int idsp_unwrap_i32_phase(void *state, const int32_t *x, int64_t *y, size_t lanes, size_t frames, int layout, void *stream)
 {
     if (int rc = check_phase_args(state, x, y, lanes, frames, layout)) return rc;
+    if (int rc = check_pair_out(y)) return rc;
     if (lanes == 0 || frames == 0) return IDSP_OK;
     return launch_stream<UnwrapProc<1>>(NoParams{0}, state, x, y, lanes, frames, layout, as_stream(stream));
 }

@@ -43,6 +43,7 @@ int idsp_sweep_i32(void *state, int32_t *out, size_t lanes, size_t frames, int l
 {
     if (layout != IDSP_FRAME_MAJOR && layout != IDSP_LANE_MAJOR) return fail(IDSP_EINVAL, "bad layout %d", layout);
     if (lanes && (!state || (frames && !out))) return fail(IDSP_EINVAL, "state or out is NULL");
+    if (reinterpret_cast<uintptr_t>(out) % 8) return fail(IDSP_EINVAL, "out holds 8-byte [re, im] pairs: it must be 8-byte aligned");
     if (lanes == 0 || frames == 0) return IDSP_OK;
     return launch_stream<SweepProc>(SweepParams{0}, state, static_cast<const int32_t *>(nullptr), reinterpret_cast<Cplx *>(out), lanes, frames,
                                     layout, as_stream(stream));

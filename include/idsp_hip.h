@@ -798,7 +798,8 @@ int idsp_clamp_wrap_i32(void *state, const int32_t *x, int32_t *y, size_t lanes,
 /* `Unwrapper<i64>` fed i32 (src/unwrap.rs:109-156).  State words per lane: { y lo, y hi }.
  *   idsp_unwrap_i32:       dx[index(f,l)] = `process(x)`, the wrapped difference to the previous sample (i32)
  *   idsp_unwrap_i32_phase: y[index(f,l)]  = `phase::<i64>()` after the sample, the unwrapped running phase (i64)
- * The two may be mixed on one state; `wraps::<i32, S>()` (:119-127) is host arithmetic on the state. */
+ * The two may be mixed on one state; `wraps::<i32, S>()` (:119-127) is host arithmetic on the state.
+ * idsp_unwrap_i32_phase: y must be 8-byte aligned (IDSP_EINVAL otherwise, nothing is written). */
 int idsp_unwrap_i32(void *state, const int32_t *x, int32_t *dx, size_t lanes, size_t frames, int layout, void *stream);
 int idsp_unwrap_i32_phase(void *state, const int32_t *x, int64_t *y, size_t lanes, size_t frames, int layout, void *stream);
 
@@ -806,7 +807,8 @@ int idsp_unwrap_i32_phase(void *state, const int32_t *x, int64_t *y, size_t lane
  * State words per lane (`PLLState`, :62-75): { clamp.x0, clamp.clamp as -1 / 0 / 1, z0, y0, f0 lo, f0 hi, f lo, f hi, y }.
  * output: IDSP_PLL_PHASE      y[index(f,l)] = `process(x)`, the output phase (:106)
  *         IDSP_PLL_FREQUENCY  y[index(f,l)] = `state.frequency()` after the sample (:84-86)
- *         IDSP_PLL_BOTH       y[index(f,l)*2 + {0: phase, 1: frequency}] (y holds 2*lanes*frames words; no in-place form)
+ *         IDSP_PLL_BOTH       y[index(f,l)*2 + {0: phase, 1: frequency}] (y holds 2*lanes*frames words, 8-byte aligned — IDSP_EINVAL
+ *                             otherwise, nothing is written; no in-place form)
  * `state.phase()` / `state.frequency()` after a call are state word 8 / state word 7. */
 #define IDSP_PLL_STATE_WORDS 9
 #define IDSP_PLL_PHASE 0
@@ -909,6 +911,7 @@ double idsp_cordic_hyperbolic_gain(void);
  * State words per lane: { state lo, state hi, accu lo, accu hi, rate, emitted lo, emitted hi }.  `emitted` counts the samples
  * produced since the state was created (it wraps): the caller sets it to 0 and reads where each lane stopped from it.
  * Output element = Complex<i32> = [re, im] adjacent, laid out as in idsp_dds_i32; both layouts, any lane and frame count.
+ * `out` must be 8-byte aligned (IDSP_EINVAL otherwise, nothing is written).
  */
 #define IDSP_SWEEP_STATE_WORDS 7
 size_t idsp_sweep_state_words(void);

@@ -2,57 +2,21 @@
 (tests/_guard.py), outputs poisoned, one state across the chunks of a call, the specification's result cached per case.
 
 Test infrastructure only."""
-import ctypes as C
 import functools
 
 import numpy as np
-import torch
 
-from tests import _harness as H
 from tests import _sweep_spec as S
-from tests._guard import Guards
+from tests._stream_proc_cases import DEV, POISON, _ptr, from_layout, run_form, to_layout  # noqa: F401  (the sweep suites use them through this module)
 
-DEV = "cuda:0"
-POISON = -77
 KERNELS = {}  # (entry, layout, lanes, frames) -> idsp_last_kernel()
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def to_layout(a, layout):
-    """[frames, lanes(, w)] -> the flat array of `layout`"""
-    return np.ascontiguousarray(a if layout == H.FM else np.swapaxes(a, 0, 1))
-
-
-def from_layout(flat, layout, frames, lanes, width):
-    a = flat.reshape((frames, lanes, width) if layout == H.FM else (lanes, frames, width))
-    return np.ascontiguousarray(a if layout == H.FM else np.swapaxes(a, 0, 1))
 
 
 def run(gpu, st, frames, layout, chunks=None):
     """The generator on state st [7, lanes] uint32 (updated).  chunks: frame counts of consecutive calls on one state.
-    Returns [frames, lanes, 2] int32."""
+    Returns [frames, lanes, 2] int32.  (The runner: tests/_stream_proc_cases.py.)"""
     lanes = st.shape[1]
-    entry = "sweep_i32"
-    gs = Guards(DEV)
-    sd = gs.upload("state", st)
-    outs, f0 = [], 0
-    for n in chunks or [frames]:
-        g = Guards(DEV)
-        yd = g.full("y", lanes * n * 2, torch.int32, POISON)
-        rc = gpu.fn[entry](_ptr(sd), _ptr(yd), lanes, n, layout, None)
-        assert rc == 0, gpu.err()
-        torch.cuda.synchronize()
-        k = KERNELS[(entry, layout, lanes, n)] = gpu.last_kernel()
-        g.check((entry, layout, lanes, n, k))
-        gs.check((entry, layout, lanes, n, k))
-        outs.append(from_layout(yd.cpu().numpy(), layout, n, lanes, 2))
-        f0 += n
-    assert f0 == frames
-    st[...] = sd.cpu().numpy().view(np.uint32)
-    return np.concatenate(outs)
+    return run_form(gpu, "sweep", None, st, None, frames, layout, chunks=chunks, record=lambda n, k: KERNELS.__setitem__(("sweep_i32", layout, lanes, n), k))
 
 
 @functools.lru_cache(maxsize=None)

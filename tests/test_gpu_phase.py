@@ -18,15 +18,15 @@ from idsp_amd import _abi
 from idsp_amd._abi import PHASE  # the feature's prototype table
 from tests import _harness as H
 from tests import _phase_spec as S
+from tests import _stream_proc_cases as SP
 from tests._guard import Guards
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-POISON = -77
+DEV, POISON, _ptr = SP.DEV, SP.POISON, SP._ptr
 
 FORMS = ["pll0", "pll1", "pll2", "unwrap0", "unwrap1", "clamp"]
-WORDS = {"pll0": 9, "pll1": 9, "pll2": 9, "unwrap0": 2, "unwrap1": 2, "clamp": 2}
-FOUR_BYTE = ["pll0", "pll1", "unwrap0", "clamp"]  # forms whose output element is 4 bytes: y == x allowed
+WORDS = {f: SP.TRAITS[f].words for f in FORMS}
+FOUR_BYTE = [f for f in FORMS if f in SP.FOUR_BYTE]  # forms whose output element is 4 bytes: y == x allowed
 KAT = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "phase_kat.json")))
 
 # every lane count of {1, 63, 64, 65, 1000, 16384, 24577, 65536, 65537} and every frame count of {1, 2, 31, 32, 33, 1000, 4096}
@@ -36,72 +36,22 @@ SHAPES = [(1, 4096), (63, 1000), (64, 33), (65, 2), (1000, 4096), (16384, 1000),
 KERNELS = {}  # (form, layout, lanes, frames) -> idsp_last_kernel()
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 def spec_run(form, ba, st, x):
     """x [frames, lanes] int32; st updated; returns [frames, lanes(, 2)]"""
-    if form.startswith("pll"):
-        return S.pll_np(ba, st, x, output=int(form[-1]))
-    if form.startswith("unwrap"):
-        return S.unwrap_np(st, x, mode=int(form[-1]))
-    return S.clamp_wrap_np(st, x)
-
-
-def to_layout(a, layout):
-    """[frames, lanes(, w)] -> the flat tensor of `layout`"""
-    return np.ascontiguousarray(a if layout == H.FM else np.swapaxes(a, 0, 1))
-
-
-def from_layout(a, layout, frames, lanes):
-    a = a.reshape((frames, lanes) + a.shape[2:]) if layout == H.FM else np.swapaxes(a.reshape((lanes, frames) + a.shape[2:]), 0, 1)
-    return np.ascontiguousarray(a)
+    return SP.spec_run(form, ba, st, x)
 
 
 def gpu_call(gpu, form, ba, sd, xd, yd, lanes, frames, layout):
-    if form.startswith("pll"):
-        rc = gpu.fn["pll_i32"]((C.c_int32 * 3)(*ba), _ptr(sd), _ptr(xd), _ptr(yd), lanes, frames, layout, int(form[-1]), None)
-    else:
-        name = {"unwrap0": "unwrap_i32", "unwrap1": "unwrap_i32_phase", "clamp": "clamp_wrap_i32"}[form]
-        rc = gpu.fn[name](_ptr(sd), _ptr(xd), _ptr(yd), lanes, frames, layout, None)
+    rc = SP.call_form(gpu, form, ba, _ptr(sd), _ptr(xd), _ptr(yd), lanes, frames, layout)
     assert rc == 0, gpu.err()
 
 
 def gpu_run(gpu, form, ba, st, x, layout, inplace=False, chunks=None):
     """x [frames, lanes] int32 (numpy); st [words, lanes] uint32, updated; returns the output as [frames, lanes(, 2)].
-    chunks: frame counts of consecutive calls on one state (their sum = frames)."""
+    chunks: frame counts of consecutive calls on one state (their sum = frames).  (The runner: tests/_stream_proc_cases.py.)"""
     frames, lanes = x.shape
-    gs = Guards(DEV)  # the state of all chunks; every buffer sits between guard bands (tests/_guard.py)
-    sd = gs.upload("state", st)
-    outs = []
-    f0 = 0
-    for n in chunks or [frames]:
-        g = Guards(DEV)
-        xd = g.upload("x", to_layout(x[f0:f0 + n], layout), readonly=not inplace)
-        if inplace:
-            assert form in FOUR_BYTE
-            yd = xd
-        elif form == "unwrap1":
-            yd = g.full("y", lanes * n, torch.int64, POISON)
-        else:
-            yd = g.full("y", lanes * n * (2 if form == "pll2" else 1), torch.int32, POISON)
-        gpu_call(gpu, form, ba, sd, xd, yd, lanes, n, layout)
-        torch.cuda.synchronize()
-        KERNELS[(form, layout, lanes, n)] = gpu.last_kernel()
-        g.check((form, layout, lanes, n, KERNELS[(form, layout, lanes, n)]))
-        gs.check((form, layout, lanes, n, KERNELS[(form, layout, lanes, n)]))
-        y = yd.cpu().numpy()
-        if form == "pll2":
-            y = y.reshape(-1, 2)
-            y = from_layout(y.reshape((n, lanes, 2) if layout == H.FM else (lanes, n, 2)), layout, n, lanes)
-        else:
-            y = from_layout(y.reshape((n, lanes) if layout == H.FM else (lanes, n)), layout, n, lanes)
-        outs.append(y)
-        f0 += n
-    assert f0 == frames
-    st[...] = sd.cpu().numpy().view(np.uint32)
-    return np.concatenate(outs)
+    return SP.run_form(gpu, form, ba, st, x, frames, layout, inplace=inplace, chunks=chunks,
+                       record=lambda n, k: KERNELS.__setitem__((form, layout, lanes, n), k))
 
 
 def case(form, lanes, frames, seed):

@@ -15,53 +15,22 @@ from idsp_amd._abi import RPLL  # the feature's prototype table
 from tests import _harness as H
 from tests import _rpll_chain as CH
 from tests import _rpll_spec as S
+from tests import _stream_proc_cases as SP
 from tests._guard import Guards
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-POISON = -77
+DEV, POISON, _ptr = SP.DEV, SP.POISON, SP._ptr
 
 # the shape list of tests/test_gpu_phase.py: every dispatch limit of launch_stream
 SHAPES = [(1, 4096), (63, 1000), (64, 33), (65, 2), (1000, 4096), (16384, 1000), (24577, 31), (65536, 32), (65537, 1), (65536, 1000), (65537, 33)]
 KERNELS = {}  # (layout, lanes, frames) -> idsp_last_kernel()
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def to_layout(a, layout):
-    """[frames, lanes, 2] -> the flat array of `layout`"""
-    return np.ascontiguousarray(a if layout == H.FM else np.swapaxes(a, 0, 1))
-
-
-def from_layout(flat, layout, frames, lanes):
-    a = flat.reshape((frames, lanes, 2) if layout == H.FM else (lanes, frames, 2))
-    return np.ascontiguousarray(a if layout == H.FM else np.swapaxes(a, 0, 1))
-
-
 def gpu_run(gpu, cfg, st, ts, layout, chunks=None):
-    """ts [frames, lanes, 2] int32; st [4, lanes] uint32, updated; chunks: frame counts of consecutive calls on one state"""
+    """ts [frames, lanes, 2] int32; st [4, lanes] uint32, updated; chunks: frame counts of consecutive calls on one state
+    (the runner: tests/_stream_proc_cases.py)"""
     frames, lanes = ts.shape[:2]
-    c = _abi.Rpll(*cfg)
-    gs = Guards(DEV)
-    sd = gs.upload("state", st)
-    outs, f0 = [], 0
-    for n in chunks or [frames]:
-        g = Guards(DEV)
-        td = g.upload("ts", to_layout(ts[f0:f0 + n], layout), readonly=True)
-        ad = g.full("accu", lanes * n * 2, torch.int32, POISON)
-        rc = gpu.fn["rpll_i32"](C.byref(c), _ptr(sd), _ptr(td), _ptr(ad), lanes, n, layout, None)
-        assert rc == 0, gpu.err()
-        torch.cuda.synchronize()
-        k = KERNELS[(layout, lanes, n)] = gpu.last_kernel()
-        g.check((cfg, layout, lanes, n, k))
-        gs.check((cfg, layout, lanes, n, k))
-        outs.append(from_layout(ad.cpu().numpy(), layout, n, lanes))
-        f0 += n
-    assert f0 == frames
-    st[...] = sd.cpu().numpy().view(np.uint32)
-    return np.concatenate(outs)
+    return SP.run_form(gpu, "rpll", cfg, st, ts, frames, layout, chunks=chunks, record=lambda n, k: KERNELS.__setitem__((layout, lanes, n), k))
 
 
 def check_case(gpu, cfg, st, ts, density=None):

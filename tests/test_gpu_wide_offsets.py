@@ -391,3 +391,133 @@ def test_cic_past_4_gib(gpu, peak, kind, dt, layout, frames, want):
     words = gpu.fn["cic_state_words"](C.byref(cfg), 64 if dt == np.int64 else 32)
     x, y = ((dt, 16, "bits"), (dt, 1)) if kind == "dec" else ((dt, 1, "bits"), (dt, 16))
     dense_subset(gpu, rng, "cic_%s_%s" % (kind, "i64" if dt == np.int64 else "i32"), cfg, words, 65536, frames, layout, x, y, want)
+
+
+# ------------------------------------------------ entries held to a numpy specification (no CPU oracle): PFB, CORDIC, batch LO, RPLL, unwrapper
+def dense_subset_np(gpu, rng, call, spec, st0, lanes, layout, xs, y, want_kernel, subset=256):
+    """`dense_subset` for the entries whose reference is a numpy specification.  xs: inputs [(dtype, frames, samples per lane and frame,
+    "bits" | "normal"), ..]; y = (dtype, frames, samples per lane and frame); st0 [words, lanes] uint32 or None.  call(state, inputs, y) -> rc on
+    device tensors; spec(state subset, [input subset [frames, n, width], ..]) -> [y frames, n, width], state subset updated.  The first `subset`
+    lanes, the last `subset` and `subset` others are compared, their state planes likewise; then the stray-write count over y's allocation."""
+    tt = {np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64, np.dtype(np.float32): torch.float32}
+
+    def buffers(dt, frames, width):
+        return wide_buffer(tt[np.dtype(dt)], frames if layout == FM else lanes, (lanes if layout == FM else frames) * width)
+
+    def gather(v, frames, width, it):  # the lanes `it` as [frames, n, width]
+        if layout == FM:
+            return v.view(frames, lanes, width)[:, it, :].cpu().numpy()
+        return np.ascontiguousarray(np.swapaxes(v[it, :].cpu().numpy().reshape(it.numel(), frames, width), 0, 1))
+
+    g = torch.Generator(device=DEV)
+    g.manual_seed(int(rng.integers(1 << 30)))
+    keep, views = [], []
+    for dt, frames, width, kind in xs:
+        xb, xv = buffers(dt, frames, width)
+        for piece in xv.reshape(-1).split((64 << 20)):  # a quarter GiB at a time: random bit patterns, or normal floats (no NaN payloads to compare)
+            if kind == "bits":
+                piece.view(torch.uint8).copy_(torch.randint(0, 256, (piece.numel() * piece.element_size(),), dtype=torch.uint8, device=DEV, generator=g))
+            else:
+                piece.copy_(torch.randn((piece.numel(),), dtype=piece.dtype, device=DEV, generator=g))
+        del piece
+        keep.append(xb), views.append(xv)
+    y_dt, y_frames, y_width = y
+    yb, yv = buffers(y_dt, y_frames, y_width)
+    sg = None if st0 is None else torch.from_numpy(st0.view(np.int32)).to(DEV)
+    rc = call(sg, views, yv)
+    torch.cuda.synchronize()
+    assert rc == 0, gpu.err()
+    kernel = gpu.last_kernel()
+    where = (lanes, layout, xs, y, kernel)
+    assert kernel.startswith(want_kernel), where
+    assert not_sentinel(yb) == not_sentinel(yv), where + ("stray writes",)
+    mid = rng.integers(subset, lanes - subset, size=subset)  # (drawn with replacement: `lanes` may be half a billion elements)
+    idx = np.unique(np.concatenate([np.arange(subset), np.arange(lanes - subset, lanes), mid]))
+    it = torch.from_numpy(idx).to(DEV)
+    so = None if st0 is None else np.ascontiguousarray(st0[:, idx])
+    want = spec(so, [gather(v, x[1], x[2], it) for v, x in zip(views, xs)])
+    got = gather(yv, y_frames, y_width, it)
+    assert got.shape == want.reshape(got.shape).shape and np.array_equal(got.view(np.uint8), np.ascontiguousarray(want).reshape(got.shape).view(np.uint8)), where
+    if st0 is not None:
+        assert np.array_equal(sg.view(st0.shape[0], lanes)[:, it].cpu().numpy().view(np.uint32), so), where + ("state",)
+    del keep, views, xv, xb, yb, yv, sg
+    torch.cuda.empty_cache()
+    return kernel
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+@pytest.mark.parametrize("layout, lanes, frames, want", [
+    (FM, 65536, 2112, "pfb_frame_major[segment 256 frames]<taps 8>"),
+    (LM, 16400, 8192, "pfb_lane_major[tile 256 frames]<taps 8>"),
+], ids=["FM", "LM"])
+def test_pfb_past_4_gib(gpu, peak, layout, lanes, frames, want):
+    """idsp_pfb_f32_process, 8 taps with the DFT, out of place: 65536 lanes x 2112 frames FrameMajor (x and y 2^32 + 2^27 bytes each) and
+    16400 lanes x 8192 frames LaneMajor (just past 2^32) — pfb_frame_major / pfb_lane_major index frames of 32 bytes on their own (pfb.h)"""
+    from tests import _pfb_spec as PF
+    from tests.test_gpu_pfb import make_cfg
+
+    rng = np.random.default_rng(30 + layout)
+    taps = 8
+    coeff = rng.standard_normal((taps, 4)).astype(np.float32)
+    cfg = make_cfg(coeff, 1)
+    st0 = PF.random_state(rng, taps, lanes)
+    dense_subset_np(gpu, rng, lambda sg, xv, yv: gpu.fn["pfb_f32_process"](C.byref(cfg), _p(sg), _p(xv[0]), _p(yv), lanes, frames, layout, None),
+                    lambda so, xi: PF.bank_np(coeff, 1, so, xi[0].reshape(frames, -1, 4, 2)), st0, lanes, layout,
+                    [(np.float32, frames, 8, "normal")], (np.float32, frames, 8), want)
+
+
+@pytest.mark.parametrize("name", ["cos_sin", "sqrt_atan2", "div"])
+def test_cordic_past_4_gib(gpu, peak, name):
+    """n = 2^29 + 2^25 + 3 elements of cordic_kernel: xy 2^32 + 2^28 + 24 bytes; a rotating and a vectoring pair-output form (out as large) and a
+    word-output form (`div`; both cos_sin and sqrt_atan2 return pairs).  Elementwise: the first 2^16, the last 2^16 and 2^16 other elements are compared"""
+    from tests import _cordic_spec as CS
+
+    n = (1 << 29) + (1 << 25) + 3
+    pair = CS.FUNCTIONS[name][2]
+    rng = np.random.default_rng(40 + pair)
+    dense_subset_np(gpu, rng, lambda sg, xv, yv: gpu.fn["cordic_%s_i32" % name](_p(xv[0]), _p(xv[1]), _p(yv), n, None),
+                    lambda so, xi: CS.function_np(name, xi[0][0], xi[1][0, :, 0]), None, n, FM,
+                    [(np.int32, 1, 2, "bits"), (np.int32, 1, 1, "bits")], (np.int32, 1, 2 if pair else 1), "cordic_kernel<%s>[four elements per thread]" % name,
+                    subset=1 << 16)
+
+
+@pytest.mark.parametrize("layout, lanes, updates, want", [
+    (FM, 1 << 20, 65, "accu_lo_kernel[FrameMajor]"),
+    (LM, 65536, 1040, "accu_lo_kernel[LaneMajor]"),
+], ids=["FM", "LM"])
+def test_accu_lo_past_4_gib(gpu, peak, layout, lanes, updates, want):
+    """idsp_accu_lo_i32 with batch_log2 = 3: `lo` of 2^20 lanes x 520 samples FrameMajor and 65536 lanes x 8320 samples LaneMajor (2^32 + 2^28 bytes) —
+    accu_lo_kernel computes `lo + r * cols * 2` and the accu index on its own (rpll.hip)"""
+    from tests import _rpll_spec as RS
+
+    k = 3
+    lo_cfg = (k, 3, 12345)
+    rng = np.random.default_rng(50 + layout)
+    dense_subset_np(gpu, rng, lambda sg, xv, yv: gpu.fn["accu_lo_i32"](C.byref(_abi.AccuLo(*lo_cfg)), _p(xv[0]), _p(yv), lanes, updates, layout, None),
+                    lambda so, xi: RS.accu_lo_np(lo_cfg, xi[0]), None, lanes, layout, [(np.int32, updates, 2, "bits")], (np.int32, updates << k, 2), want)
+
+
+def test_rpll_frame_major_past_4_gib(gpu, peak):
+    """idsp_rpll_i32, FrameMajor, 2^20 lanes x 520 frames (ts and accu 2^32 + 2^28 bytes each): the only 8-byte-in processor on the register-window
+    stream kernel at a large lane count"""
+    from tests import _rpll_spec as RS
+
+    lanes, frames, cfg = 1 << 20, 520, (8, 23, 22)
+    rng = np.random.default_rng(60)
+    dense_subset_np(gpu, rng, lambda sg, xv, yv: gpu.fn["rpll_i32"](C.byref(_abi.Rpll(*cfg)), _p(sg), _p(xv[0]), _p(yv), lanes, frames, FM, None),
+                    lambda so, xi: RS.rpll_np(cfg, so, xi[0]), RS.random_state(rng, lanes), lanes, FM, [(np.int32, frames, 2, "bits")], (np.int32, frames, 2),
+                    "stream_frame_major<idsp::(anonymous namespace)::RpllProc>")
+
+
+def test_unwrap_phase_frame_major_past_4_gib(gpu, peak):
+    """idsp_unwrap_i32_phase, FrameMajor, 2^20 lanes x 520 frames: 4-byte rows in, 8-byte rows out (y 2^32 + 2^28 bytes) on the register-window kernel"""
+    from tests import _phase_spec as PS
+
+    lanes, frames = 1 << 20, 520
+    rng = np.random.default_rng(61)
+    dense_subset_np(gpu, rng, lambda sg, xv, yv: gpu.fn["unwrap_i32_phase"](_p(sg), _p(xv[0]), _p(yv), lanes, frames, FM, None),
+                    lambda so, xi: PS.unwrap_np(so, xi[0][:, :, 0], mode=1)[:, :, None], PS.random_state(rng, 2, lanes), lanes, FM,
+                    [(np.int32, frames, 1, "bits")], (np.int64, frames, 1), "stream_frame_major<idsp::(anonymous namespace)::UnwrapProc<1>>")
