@@ -380,6 +380,7 @@ RPLL = {
     "rpll_state_words": (_SZ, []),
     "rpll_i32": (_I, [_P, _P, _P, _P, _SZ, _SZ, _I, _P]),  # cfg, state, ts, accu, lanes, frames, layout, stream
     "accu_lo_i32": (_I, [_P, _P, _P, _SZ, _SZ, _I, _P]),   # cfg, accu, lo, lanes, updates, layout, stream
+    "lockin_i32_accu_process": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _SZ, _I, _P]),  # cfg, lo_cfg, state, x, accu, y, lanes, updates, layout, stream
 }
 UTILS.update(RPLL)
 

@@ -132,6 +132,21 @@ inline int check_stream_args(const void *cfg, size_t n, const void *state, const
     return IDSP_OK;
 }
 
+// bytes of n0 * n1 elements of `elem` bytes, saturating: check_stream_args admits lane and frame counts whose product leaves size_t
+inline size_t span_bytes(size_t n0, size_t n1, size_t elem)
+{
+    size_t n = 0;
+    if (__builtin_mul_overflow(n0, n1, &n) || __builtin_mul_overflow(n, elem, &n)) return SIZE_MAX;
+    return n;
+}
+// [a, a + an) and [b, b + bn) share a byte; a range that would run past the end of the address space ends there
+inline bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn)
+{
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    const uintptr_t ea = an > UINTPTR_MAX - pa ? UINTPTR_MAX : pa + an, eb = bn > UINTPTR_MAX - pb ? UINTPTR_MAX : pb + bn;
+    return pa < eb && pb < ea;
+}
+
 // Workgroup barrier that orders LDS traffic only.  HIP's __syncthreads() also
 // drains vmcnt (all global loads AND stores of the wave), which serialises
 // every register prefetch and every output store behind the next barrier; the

@@ -34,6 +34,8 @@
 //   consecutive frames back to back, which gives the scheduler independent
 //   dependency chains to interleave — at one wave per SIMD the per-frame
 //   dependent-chain latency, not throughput, is what bounds these kernels.
+//   Within one call every kernel here runs a lane's whole batches first and its remaining frames one by one (pre()) after them,
+//   never a batch after a single frame: lockin_accu_procs.h relies on that order.
 //   static constexpr int IN_DIV;      FRAME_MAJOR only: IN_DIV adjacent threads
 //   ("virtual lanes") share one input lane — used to split the I and Q arms of
 //   the lock-in / DDS over two threads when there are too few lanes to give
@@ -1600,8 +1602,8 @@ template <class T, class = void>
 struct HasCoefPlanes : std::false_type {};
 template <class T>
 struct HasCoefPlanes<T, std::void_t<decltype(std::declval<T>().coef)>> : std::true_type {};
-// (parameters that carry a per-lane side pointer — lockin_generic.hip's XWalk `xw`, computed from the lane index of the WHOLE call —
-// cannot be shifted here: launch_stream's lane splits only take 4-byte-in / 4-byte-out processors, and this assert keeps it so)
+// (parameters that carry a per-lane side pointer under the name `xw` — lockin_generic.hip's XWalk, lockin_accu_procs.h's AccuWalk, both
+// computed from the lane index of the WHOLE call — cannot be shifted here: launch_stream's lane splits only take 4-byte-in / 4-byte-out processors, and this assert keeps it so)
 template <class T, class = void>
 struct HasSideWalk : std::false_type {};
 template <class T>
@@ -1609,7 +1611,7 @@ struct HasSideWalk<T, std::void_t<decltype(std::declval<T>().xw)>> : std::true_t
 template <class Params>
 inline Params shift_lanes(Params p, size_t first, size_t elem)
 {
-    static_assert(!HasSideWalk<Params>::value, "lane split of a processor whose parameters hold a side pointer (XWalk): shift it here first");
+    static_assert(!HasSideWalk<Params>::value, "lane split of a processor whose parameters hold a side pointer `xw` (XWalk, AccuWalk): shift it here first");
     if constexpr (HasCoefPlanes<Params>::value) p.coef = static_cast<const char *>(p.coef) + first * elem;
     return p;
 }

@@ -102,22 +102,6 @@ int launch_accu_lo(const idsp_accu_lo *cfg, const int32_t *accu, int32_t *lo, si
     return launch_status();
 }
 
-// bytes of n0 * n1 8-byte pairs, saturating: check_stream_args admits lane and frame counts whose product leaves size_t
-size_t pair_bytes(size_t n0, size_t n1)
-{
-    size_t n = 0;
-    if (__builtin_mul_overflow(n0, n1, &n) || __builtin_mul_overflow(n, size_t(8), &n)) return SIZE_MAX;
-    return n;
-}
-
-// [a, a + an) and [b, b + bn) share a byte; a range that would run past the end of the address space ends there
-bool overlap(const void *a, size_t an, const void *b, size_t bn)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    const uintptr_t ea = an > UINTPTR_MAX - pa ? UINTPTR_MAX : pa + an, eb = bn > UINTPTR_MAX - pb ? UINTPTR_MAX : pb + bn;
-    return pa < eb && pb < ea;
-}
-
 }  // namespace
 }  // namespace idsp
 
@@ -141,7 +125,7 @@ int idsp_rpll_i32(const idsp_rpll *cfg, void *state, const int32_t *ts, int32_t 
     if (lanes == 0 || frames == 0) return IDSP_OK;
     if (!state) return fail(IDSP_EINVAL, "state is NULL");
     if ((reinterpret_cast<uintptr_t>(ts) | reinterpret_cast<uintptr_t>(accu)) % 8) return fail(IDSP_EINVAL, "ts and accu hold 8-byte pairs: they must be 8-byte aligned");
-    if (overlap(ts, pair_bytes(lanes, frames), accu, pair_bytes(lanes, frames))) return fail(IDSP_EINVAL, "ts and accu overlap");
+    if (ranges_overlap(ts, span_bytes(lanes, frames, 8), accu, span_bytes(lanes, frames, 8))) return fail(IDSP_EINVAL, "ts and accu overlap");
     RpllParams p;
     p.dt2 = cfg->dt2, p.sf = cfg->shift_frequency, p.sdy = cfg->shift_phase - cfg->dt2;
     p.half = uint32_t(1) << (cfg->shift_frequency - 1);
@@ -159,7 +143,7 @@ int idsp_accu_lo_i32(const idsp_accu_lo *cfg, const int32_t *accu, int32_t *lo, 
     if (int rc = check_stream_args(nullptr, 0, nullptr, accu, lo, lanes, frames, layout)) return rc;
     if (lanes == 0 || updates == 0) return IDSP_OK;
     if ((reinterpret_cast<uintptr_t>(accu) | reinterpret_cast<uintptr_t>(lo)) % 8) return fail(IDSP_EINVAL, "accu and lo hold 8-byte pairs: they must be 8-byte aligned");
-    if (overlap(accu, pair_bytes(lanes, updates), lo, pair_bytes(lanes, frames))) return fail(IDSP_EINVAL, "accu and lo overlap");
+    if (ranges_overlap(accu, span_bytes(lanes, updates, 8), lo, span_bytes(lanes, frames, 8))) return fail(IDSP_EINVAL, "accu and lo overlap");
     if (layout == IDSP_LANE_MAJOR) return launch_accu_lo<true>(cfg, accu, lo, lanes, updates, as_stream(stream));
     return launch_accu_lo<false>(cfg, accu, lo, lanes, updates, as_stream(stream));
 }

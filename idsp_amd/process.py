@@ -26,7 +26,8 @@ own:
     PolyphaseBank (* Dft4), prototype()  (examples/polyphase_channelizer.rs) PolyphaseBank.prototype(taps).lanes(N)
     overflowing_sub / saturating_scale   (unwrap.rs:73-101) overflowing_sub(y, x), saturating_scale(lo, hi, shift)
     Sweep / AccuOsc<Sweep>               (sweptsine.rs:12-188) Sweep.fit(stop, harmonics, cycles), SweepOsc(N, rate, state)
-    RPLLConfig / RPLL, the returned Accu (rpll.rs:13-90, accu.rs:34-54) RPLLConfig(dt2, sf, sp).lanes(N), accu_lo(accu, lo, ...)
+    RPLLConfig / RPLL, the returned Accu (rpll.rs:13-90, accu.rs:34-54) RPLLConfig(dt2, sf, sp).lanes(N), accu_lo(accu, lo, ...),
+                                                          LockinLo(...).process_accu(x, accu, y, batch_log2, harmonic)
     cossin(phase)                        (cossin.rs:14)  cossin(phases)
     atan2(y, x) / Complex::arg           (atan2.rs:66)   atan2(xy)
     cordic::{cos_sin, sqrt_atan2, ...}   (cordic.rs:80-107) cordic_cos_sin(xy, z), cordic_sqrt_atan2(xy, z), ...
@@ -837,6 +838,28 @@ class LockinLo:
         head = (C.byref(self.cfg),) if self.n is None else (C.cast(self.cfg, C.c_void_p), self.n)
         call(self._entry, *head, C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(lo.data_ptr()),
              C.c_void_p(y.data_ptr()), self.n_lanes, frames, layout, _stream_ptr(x))
+        return y
+
+    def process_accu(self, x: torch.Tensor, accu: torch.Tensor, y: torch.Tensor, batch_log2: int, harmonic: int = 1, offset: int = 0,
+                     layout: int = FrameMajor):
+        """`accu_lo(accu, lo, ...)` followed by `process(x, lo, y)` in one kernel, the LO never stored
+        (idsp_lockin_i32_accu_process; `[Lowpass<N>; K]` arms only).  accu holds `updates` rows of {state, step} pairs per lane as
+        `RPLLLanes.process` writes them, x `updates << batch_log2` samples per lane, y a trailing [re, im] pair per sample; the
+        state is this object's, so `process` and `process_accu` calls may follow each other mid-stream."""
+        if self.n is not None:
+            raise ValueError("process_accu: [Lowpass<N>; K] arms only")
+        if not 0 <= int(batch_log2) <= 24:
+            raise ValueError("batch_log2 must be in 0..=24")
+        for t, what in ((x, "x"), (accu, "accu"), (y, "y")):
+            _check(t, torch.int32, what)
+        if accu.numel() % (2 * max(self.n_lanes, 1)):
+            raise ValueError("accu.len() must be updates * lanes * 2")
+        updates = accu.numel() // (2 * self.n_lanes) if self.n_lanes else 0
+        if x.numel() != (updates << batch_log2) * self.n_lanes or y.numel() != 2 * x.numel():
+            raise ValueError("x.len() must be (updates << batch_log2) * lanes and y.len() twice that")
+        lo_cfg = _abi.AccuLo(int(batch_log2), _i32(harmonic), _i32(offset))
+        call("lockin_i32_accu_process", C.byref(self.cfg), C.byref(lo_cfg), C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()),
+             C.c_void_p(accu.data_ptr()), C.c_void_p(y.data_ptr()), self.n_lanes, updates, layout, _stream_ptr(x))
         return y
 
 

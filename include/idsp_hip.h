@@ -1003,6 +1003,29 @@ typedef struct idsp_accu_lo {
 int idsp_accu_lo_i32(const idsp_accu_lo *cfg, const int32_t *accu, int32_t *lo, size_t lanes, size_t updates, int layout,
                      void *stream);
 
+/* idsp_accu_lo_i32 followed by idsp_lockin_i32_lo_process, with the LO never stored: the lock-in with `[Lowpass<N>; K]` arms
+ * (src/lockin.rs:17-39) whose LO is iterated inside the kernel from the `Accu` rows (src/accu.rs:34-54, `Complex::from_angle`
+ * src/complex.rs:237-240).  y and the state are bit for bit those of
+ *     idsp_accu_lo_i32(lo_cfg, accu, lo, lanes, updates, layout, stream);
+ *     idsp_lockin_i32_lo_process(cfg, state, x, lo, y, lanes, updates << lo_cfg->batch_log2, layout, stream);
+ * without the 8 bytes per sample of `lo` being written and read again (nor allocated: 2 GiB at 65536 lanes x 4096 frames).
+ *   x     frames = updates << batch_log2 i32 samples per lane
+ *   accu  `updates` rows of { state, step } pairs per lane, as idsp_rpll_i32 writes them
+ *   y     frames `Complex<i32>` [re, im] per lane
+ * all three in `layout`, as the two entries above define it.  State: the two arms only, idsp_lockin_state_words(cfg) - 2 words
+ * per lane — the state of idsp_lockin_i32_lo_process, and the two entries may be mixed on one state mid-stream.  Read at entry,
+ * written at exit: consecutive calls on update ranges equal one long call.
+ * IDSP_EINVAL (and nothing written) unless cfg has order 1..2 and cascade 1..IDSP_LOCKIN_MAX_CASCADE, 0 <= batch_log2 <= 24,
+ * updates << batch_log2 <= 2^40, accu and y are 8-byte aligned and x, accu and y are pairwise disjoint (no in-place form: x is 4
+ * bytes per sample and y 8).  lanes == 0 or updates == 0 is IDSP_OK.
+ * When to prefer it (MI355X, 4096 output frames, k = 3, three low-pass shapes; profiles/NOTES.md, "Lock-in on Accu rows"): at 65536
+ * lanes it takes 0.46-0.52 of the chain's time FrameMajor and 0.64-0.69 LaneMajor, at 32768 lanes 0.77-0.85 and 0.95-0.97.  At 16384
+ * lanes the CHAIN is the faster route: this entry takes 1.08-1.22 x its time FrameMajor and 1.22-1.32 x LaneMajor.  The chain's
+ * lock-in runs the multi-wave kernels and this entry has no multi-wave form; at that lane count the bytes it saves no longer pay
+ * for the difference.  Where between 16384 and 32768 lanes the two cross was not measured.  What it always saves is the LO buffer. */
+int idsp_lockin_i32_accu_process(const idsp_lockin_i32 *cfg, const idsp_accu_lo *lo_cfg, void *state, const int32_t *x,
+                                 const int32_t *accu, int32_t *y, size_t lanes, size_t updates, int layout, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* lane split over several devices in ONE process: idsp_multi_*             */
 /* ------------------------------------------------------------------------ */

@@ -1334,6 +1334,19 @@ struct AccuLo {
         const idsp_accu_lo cfg{batch_log2, harmonic, offset};
         check(idsp_accu_lo_i32(&cfg, accu.flat, lo.flat, accu.lanes, accu.frames, Layout::value, stream));
     }
+    /// `process_view` followed by the external-LO lock-in with `[Lowpass<N>; K]` arms (idsp_lockin_i32_lo_process) in one kernel,
+    /// the LO never stored (idsp_lockin_i32_accu_process).  arms: order, cascade and gains; state: the two arms,
+    /// `idsp_lockin_state_words(&arms) - 2` words per lane, shared with idsp_lockin_i32_lo_process; x: `updates << batch_log2`
+    /// samples per lane; y: [re, im] per sample (accu and y with width 2).
+    template <class Layout>
+    void lockin_view(const idsp_lockin_i32 &arms, DeviceBuffer<uint32_t> &state, View<int32_t, Layout> x, View<int32_t, Layout> accu,
+                     ViewMut<int32_t, Layout> y, void *stream = nullptr) const
+    {
+        require(x.lanes == accu.lanes && y.lanes == accu.lanes && x.frames == accu.frames << batch_log2 && y.frames == x.frames, "view shape mismatch");
+        require(idsp_lockin_state_words(&arms) >= 2 && state.len() == (idsp_lockin_state_words(&arms) - 2) * accu.lanes, "state: the two arms per lane");
+        const idsp_accu_lo cfg{batch_log2, harmonic, offset};
+        check(idsp_lockin_i32_accu_process(&arms, &cfg, state.data(), x.flat, accu.flat, y.flat, accu.lanes, accu.frames, Layout::value, stream));
+    }
 };
 
 }  // namespace idsp_hip

@@ -1,0 +1,287 @@
+"""idsp_lockin_i32_accu_process on the GPU, through the C ABI: idsp_accu_lo_i32 followed by idsp_lockin_i32_lo_process with the LO
+never stored.  Against the specification (tests/_lockin_accu_cases.py: accu_lo_np fed to the checker library's lock-in, held to a
+per-sample Python-integer walk in tests/test_lockin_accu_spec.py) and against the two chain entries on the device.
+
+Every output word and every state word is compared with array_equal; outputs start poisoned, every buffer sits between guard
+bands, the inputs are held read-only, the state starts from random words."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from idsp_amd import _abi
+from idsp_amd._abi import RPLL  # the table that holds the feature's prototype
+from tests import _harness as H
+from tests import _lockin_accu_cases as LA
+from tests import _rpll_chain as CH
+from tests import _rpll_spec as S
+from tests._guard import Guards
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+POISON = -77
+KERNELS = {}
+ENTRY = "lockin_i32_accu_process"
+
+LANES = [1, 63, 64, 65, 1000]
+UPDATES = [1, 3, 33]
+KS = [0, 1, 3, 10]
+SPLIT_MAX = 40960  # kSplitMaxLanes (idsp_amd/csrc/dds_dev.h): the I and Q arms on two threads up to here
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def to_layout(a, layout):
+    """[frames, lanes(, 2)] -> the layout's order"""
+    return np.ascontiguousarray(a if layout == H.FM else np.swapaxes(a, 0, 1))
+
+
+def from_layout(flat, layout, frames, lanes):
+    a = flat.reshape((frames, lanes, 2) if layout == H.FM else (lanes, frames, 2))
+    return np.ascontiguousarray(a if layout == H.FM else np.swapaxes(a, 0, 1))
+
+
+def fused(gpu, cfg, lo_cfg, sd, xd, ad, yd, lanes, updates, layout):
+    rc = gpu.fn[ENTRY](C.byref(cfg), C.byref(_abi.AccuLo(*lo_cfg)), _ptr(sd), _ptr(xd), _ptr(ad), _ptr(yd), lanes, updates, layout, None)
+    assert rc == 0, gpu.err()
+    KERNELS[(layout, lanes, updates, lo_cfg[0], cfg.order, cfg.cascade)] = gpu.last_kernel()
+
+
+def chain(gpu, cfg, lo_cfg, sd, xd, ad, lod, yd, lanes, updates, layout):
+    assert gpu.fn["accu_lo_i32"](C.byref(_abi.AccuLo(*lo_cfg)), _ptr(ad), _ptr(lod), lanes, updates, layout, None) == 0, gpu.err()
+    assert gpu.fn["lockin_i32_lo_process"](C.byref(cfg), _ptr(sd), _ptr(xd), _ptr(lod), _ptr(yd), lanes, updates << lo_cfg[0], layout, None) == 0, gpu.err()
+
+
+def gpu_run(gpu, ks, lo_cfg, st, x, accu, layout, offs=(0, 0, 0), ranges=None, via_chain=()):
+    """One call, or one call per update range in `ranges` on one state (those whose index is in `via_chain` through the two chain
+    entries).  offs: bytes between the 512-byte grid and x, accu, y.  -> (y [frames, lanes, 2], state after [words, lanes] uint32)"""
+    frames, lanes = x.shape
+    updates, k = accu.shape[0], lo_cfg[0]
+    cfg = H.lockin_cfg(ks)
+    g = Guards(DEV)
+    sd = g.upload("state", st)
+    ys = []
+    for i, (u0, u1) in enumerate(ranges or [(0, updates)]):
+        xd = g.upload("x", to_layout(x[u0 << k:u1 << k], layout), off=offs[0], readonly=True)
+        ad = g.upload("accu", to_layout(accu[u0:u1], layout), off=offs[1], readonly=True)
+        yd = g.full("y", ((u1 - u0) << k) * lanes * 2, torch.int32, POISON, off=offs[2])
+        if i in via_chain:
+            chain(gpu, cfg, lo_cfg, sd, xd, ad, g.full("lo", ((u1 - u0) << k) * lanes * 2, torch.int32, POISON), yd, lanes, u1 - u0, layout)
+        else:
+            fused(gpu, cfg, lo_cfg, sd, xd, ad, yd, lanes, u1 - u0, layout)
+        ys.append((yd, (u1 - u0) << k))
+    torch.cuda.synchronize()
+    g.check((ENTRY, ks, lo_cfg, layout, lanes, updates, offs, ranges, gpu.last_kernel()))
+    y = np.concatenate([from_layout(yd.cpu().numpy(), layout, n, lanes) for yd, n in ys])
+    return y, sd.cpu().numpy().view(np.uint32).reshape(st.shape)
+
+
+def case(rng, order, cascade, lanes, updates, k, h=None):
+    ks = LA.lowpass_ks(rng, order, cascade)
+    lo_cfg = (k, S.LO_HARMONICS[int(rng.integers(len(S.LO_HARMONICS)))] if h is None else h, int(rng.integers(-(1 << 31), 1 << 31)))
+    return ks, lo_cfg, LA.random_state(rng, order, cascade, lanes), LA.adversarial_x(rng, updates << k, lanes), S.adversarial_accu(rng, updates, lanes)
+
+
+@pytest.mark.parametrize("lanes", LANES)
+@pytest.mark.parametrize("updates", UPDATES)
+def test_equals_the_spec(gpu, lanes, updates):
+    """k and the harmonic walk their grids, the eight (order, cascade) shapes are spread over the (lanes, updates, k) grid and each
+    runs in both layouts; bases at 0 and 8 mod 16"""
+    rng = np.random.default_rng(1000 * updates + lanes)
+    ks_ = [k for k in KS if (updates << k) * lanes <= 1 << 22]
+    assert ks_[-1] == 10 or lanes * updates > 1 << 12
+    for i, k in enumerate(ks_):
+        order, cascade = LA.SHAPES[(LANES.index(lanes) + 5 * UPDATES.index(updates) + 3 * i) % 8]
+        h = S.LO_HARMONICS[(i + lanes + updates) % len(S.LO_HARMONICS)]
+        ks, lo_cfg, st, x, accu = case(rng, order, cascade, lanes, updates, k, h)
+        sw = st.copy()
+        want = LA.spec(ks, lo_cfg, sw, x, accu)
+        for layout in (H.FM, H.LM):
+            for offs in ((0, 0, 0), (8, 8, 8)) if i % 2 == 0 else ((0, 8, 0), (8, 0, 8)):
+                y, sg = gpu_run(gpu, ks, lo_cfg, st, x, accu, layout, offs)
+                assert np.array_equal(y, want) and np.array_equal(sg, sw), (order, cascade, lo_cfg, layout, lanes, updates, offs, gpu.last_kernel())
+
+
+def test_every_shape_in_both_layouts(gpu):
+    """the grid above spreads the shapes; this holds each of the eight in both layouts, at a lane count with a ragged last wave"""
+    for order, cascade in LA.SHAPES:
+        rng = np.random.default_rng(10 * order + cascade)
+        ks, lo_cfg, st, x, accu = case(rng, order, cascade, 130, 5, 3)
+        sw = st.copy()
+        want = LA.spec(ks, lo_cfg, sw, x, accu)
+        for layout in (H.FM, H.LM):
+            y, sg = gpu_run(gpu, ks, lo_cfg, st, x, accu, layout)
+            assert np.array_equal(y, want) and np.array_equal(sg, sw), (order, cascade, lo_cfg, layout)
+
+
+@pytest.mark.parametrize("lanes", [SPLIT_MAX, SPLIT_MAX + 1])
+def test_the_split_boundary(gpu, lanes):
+    """the arms on two threads up to kSplitMaxLanes, one thread per lane above: both against the spec, and by name"""
+    rng = np.random.default_rng(lanes)
+    ks, lo_cfg, st, x, accu = case(rng, 2, 2, lanes, 2, 2)
+    sw = st.copy()
+    want = LA.spec(ks, lo_cfg, sw, x, accu)
+    for layout in (H.FM, H.LM):
+        y, sg = gpu_run(gpu, ks, lo_cfg, st, x, accu, layout)
+        k = gpu.last_kernel()
+        assert ("LockinAccuSplitProc<2, 2>" in k) == (lanes <= SPLIT_MAX) and ("LockinAccuProc<2, 2>" in k) == (lanes > SPLIT_MAX), (lanes, layout, k)
+        assert np.array_equal(y, want) and np.array_equal(sg, sw), (lanes, layout, k)
+
+
+@pytest.mark.parametrize("k,updates", [(3, 9), (2, 17), (1, 36), (0, 70)])
+def test_one_thread_processor_in_its_batched_loops(gpu, k, updates):
+    """Above kSplitMaxLanes with enough frames for the batched loops of both kernels (stream_frame_major's window loop needs 48
+    frames, stream_lane_major's a full tile of 32), and a tail behind them: LockinAccuProc::pre_batch with the rotating x window
+    around it.  k = 3: one pair per batch; k = 2, 1, 0: two, four and eight reloads per batch from the per-frame pairs."""
+    lanes = SPLIT_MAX + 1
+    assert 48 < (updates << k) < 96 and (updates << k) % 32
+    rng = np.random.default_rng(50 + k)
+    ks, lo_cfg, st, x, accu = case(rng, 1 + k % 2, 1 + k % 3, lanes, updates, k)
+    sw = st.copy()
+    want = LA.spec(ks, lo_cfg, sw, x, accu)
+    for layout in (H.FM, H.LM):
+        y, sg = gpu_run(gpu, ks, lo_cfg, st, x, accu, layout)
+        assert "LockinAccuProc<" in gpu.last_kernel(), gpu.last_kernel()
+        assert np.array_equal(y, want) and np.array_equal(sg, sw), (k, updates, layout, gpu.last_kernel())
+
+
+@pytest.mark.parametrize("lanes", [130, 1000])
+def test_two_reloads_per_batch(gpu, lanes):
+    """k = 2 on the split processor with batches in both layouts (52 frames: a window loop and a full tile, then a tail)"""
+    rng = np.random.default_rng(60 + lanes)
+    ks, lo_cfg, st, x, accu = case(rng, 2, 2, lanes, 13, 2)
+    sw = st.copy()
+    want = LA.spec(ks, lo_cfg, sw, x, accu)
+    for layout in (H.FM, H.LM):
+        y, sg = gpu_run(gpu, ks, lo_cfg, st, x, accu, layout)
+        assert np.array_equal(y, want) and np.array_equal(sg, sw), (lanes, layout, gpu.last_kernel())
+
+
+@pytest.mark.parametrize("k", [0, 3])
+def test_equals_the_device_chain(gpu, k):
+    """accu_lo_i32 -> lockin_i32_lo_process and the fused entry on the same device buffers from the same initial state"""
+    lanes, updates = 130, 9
+    for layout in (H.FM, H.LM):
+        rng = np.random.default_rng(20 + k + layout)
+        ks, lo_cfg, st, x, accu = case(rng, 1 + (k + layout) % 2, 3, lanes, updates, k)
+        cfg = H.lockin_cfg(ks)
+        frames = updates << k
+        g = Guards(DEV)
+        xd = g.upload("x", to_layout(x, layout), readonly=True)
+        ad = g.upload("accu", to_layout(accu, layout), readonly=True)
+        s1, s2 = g.upload("state (chain)", st), g.upload("state (fused)", st)
+        lod = g.full("lo", frames * lanes * 2, torch.int32, POISON)
+        y1, y2 = g.full("y (chain)", frames * lanes * 2, torch.int32, POISON), g.full("y (fused)", frames * lanes * 2, torch.int32, POISON + 1)
+        chain(gpu, cfg, lo_cfg, s1, xd, ad, lod, y1, lanes, updates, layout)
+        fused(gpu, cfg, lo_cfg, s2, xd, ad, y2, lanes, updates, layout)
+        torch.cuda.synchronize()
+        g.check(("chain and " + ENTRY, k, layout))
+        assert torch.equal(y1, y2) and torch.equal(s1, s2), (k, layout)
+        assert not torch.equal(s1.cpu(), torch.from_numpy(st.view(np.int32)))
+
+
+def test_chunks(gpu):
+    """uneven update ranges carried on one state equal one call"""
+    for k, layout in ((3, H.FM), (3, H.LM), (1, H.FM), (0, H.LM)):
+        rng = np.random.default_rng(30 + k + layout)
+        ks, lo_cfg, st, x, accu = case(rng, 2, 1, 130, 9, k)
+        whole, sw = gpu_run(gpu, ks, lo_cfg, st, x, accu, layout)
+        parts, sp = gpu_run(gpu, ks, lo_cfg, st, x, accu, layout, ranges=[(0, 1), (1, 7), (7, 9)])
+        assert np.array_equal(whole, parts) and np.array_equal(sw, sp), (k, layout)
+        s0 = st.copy()
+        assert np.array_equal(whole, LA.spec(ks, lo_cfg, s0, x, accu)) and np.array_equal(sw, s0), (k, layout)
+
+
+def test_state_hand_over(gpu):
+    """the first half through the fused entry, the second through accu_lo_i32 -> lockin_i32_lo_process on the same state: one fused call"""
+    for layout in (H.FM, H.LM):
+        rng = np.random.default_rng(40 + layout)
+        ks, lo_cfg, st, x, accu = case(rng, 1, 4, 130, 8, 3)
+        whole, sw = gpu_run(gpu, ks, lo_cfg, st, x, accu, layout)
+        for via in ((1,), (0,)):
+            parts, sp = gpu_run(gpu, ks, lo_cfg, st, x, accu, layout, ranges=[(0, 4), (4, 8)], via_chain=via)
+            assert np.array_equal(whole, parts) and np.array_equal(sw, sp), (layout, via)
+
+
+def test_reference_locked_chain(gpu):
+    """tests/_rpll_chain.py's case with idsp_rpll_i32 -> the fused entry, once per harmonic: bit-equal to the spec's LO fed to the
+    checker library's lock-in, and atan2(mean Q, mean I) over the last quarter within the 1e-2 rad of -phi that
+    test_gpu_rpll.py::test_chain_on_the_device holds the unfused chain to"""
+    c = CH.chain()
+    lanes, updates, frames = CH.LANES, CH.UPDATES, c["frames"]
+    lc = CH.lockin_cfg()
+    worst = 0.0
+    for hh in CH.HARMONICS:
+        g = Guards(DEV)
+        td = g.upload("ts", c["ts"], readonly=True)
+        xd = g.upload("x", c["x"], readonly=True)
+        rd = g.full("rpll state", 4 * lanes, torch.int32, 0)
+        ld = g.full("arm state", 4 * lanes, torch.int32, 0)
+        ad = g.full("accu", updates * lanes * 2, torch.int32, POISON)
+        yd = g.full("y", frames * lanes * 2, torch.int32, POISON)
+        assert gpu.fn["rpll_i32"](C.byref(_abi.Rpll(*CH.CFG)), _ptr(rd), _ptr(td), _ptr(ad), lanes, updates, H.FM, None) == 0, gpu.err()
+        fused(gpu, lc, (CH.K, hh, 0), ld, xd, ad, yd, lanes, updates, H.FM)
+        torch.cuda.synchronize()
+        g.check(("rpll_i32 -> " + ENTRY, hh))
+        assert np.array_equal(ad.cpu().numpy().reshape(updates, lanes, 2), c["accu"])
+        y = yd.cpu().numpy().reshape(frames, lanes, 2)
+        assert np.array_equal(y, c["want"][hh]), hh
+        assert np.array_equal(ld.cpu().numpy().view(np.uint32).reshape(4, lanes), c["arms"][hh])
+        worst = max(worst, CH.phase_error(c, hh, y).max())
+    print("reference-locked chain on the fused entry: worst |arg + phi|", worst)
+    assert worst <= 1e-2, worst
+
+
+def test_rejected_calls_write_nothing(gpu):
+    rng = np.random.default_rng(5)
+    lanes, updates, k = 64, 4, 3
+    frames = updates << k
+    g = Guards(DEV)
+    xd = g.upload("x", LA.adversarial_x(rng, frames + 2, lanes), readonly=True)
+    ad = g.upload("accu", S.adversarial_accu(rng, updates + 1, lanes), readonly=True)
+    sd = g.upload("state", LA.random_state(rng, 2, 2, lanes))
+    yd = g.full("y", (frames + 1) * lanes * 2, torch.int32, POISON)
+    g.freeze("state"), g.freeze("y")
+    good, lo = H.lockin_cfg(LA.lowpass_ks(rng, 2, 2)), _abi.AccuLo(k, 1, 0)
+    X, A, Y, S_ = xd.data_ptr(), ad.data_ptr(), yd.data_ptr(), sd.data_ptr()
+
+    def rejected(cfg, lo_cfg, x=X, a=A, y=Y, layout=H.FM, why=""):
+        rc = gpu.fn[ENTRY](C.byref(cfg) if cfg is not None else None, C.byref(lo_cfg) if lo_cfg is not None else None, C.c_void_p(S_), C.c_void_p(x),
+                           C.c_void_p(a), C.c_void_p(y), lanes, updates, layout, None)
+        assert rc == _abi.IDSP_EINVAL and gpu.err(), (why, rc)
+
+    for layout in (H.FM, H.LM):
+        rejected(None, lo, layout=layout, why="cfg NULL")
+        rejected(good, None, layout=layout, why="lo_cfg NULL")
+        for bad in (-1, 25):
+            rejected(good, _abi.AccuLo(bad, 1, 0), layout=layout, why=("batch_log2", bad))
+        rejected(good, lo, a=A + 4, layout=layout, why="accu at 4 mod 8")
+        rejected(good, lo, y=Y + 4, layout=layout, why="y at 4 mod 8")
+        rejected(good, lo, x=Y + 8 * lanes, layout=layout, why="x overlaps y")
+        rejected(good, lo, a=Y + 8 * lanes, layout=layout, why="accu overlaps y")
+        rejected(good, lo, a=X + 8, layout=layout, why="accu overlaps x")
+    rejected(good, lo, layout=7, why="layout")
+    for order, cascade in ((0, 1), (3, 1), (1, 0), (1, 5)):
+        bad = H.lockin_cfg(LA.lowpass_ks(rng, 2, 2))
+        bad.order, bad.cascade = order, cascade
+        rejected(bad, lo, why=("order, cascade", order, cascade))
+    # nothing to do is not an error, wherever the pointers of the empty buffers point
+    for n_l, n_u in ((0, updates), (lanes, 0)):
+        for a_p, y_p in ((A, Y), (A + 4, Y + 4), (Y, Y)):
+            assert gpu.fn[ENTRY](C.byref(good), C.byref(lo), C.c_void_p(S_), C.c_void_p(X), C.c_void_p(a_p), C.c_void_p(y_p), n_l, n_u, H.FM, None) == 0, gpu.err()
+    torch.cuda.synchronize()
+    g.check("rejected " + ENTRY + " calls")
+
+
+def test_dispatch(gpu):
+    """which kernel each (layout, lanes, updates, k, order, cascade) took"""
+    if not KERNELS:
+        ks, lo_cfg, st, x, accu = case(np.random.default_rng(0), 1, 1, 65, 3, 3)
+        gpu_run(gpu, ks, lo_cfg, st, x, accu, H.FM)
+    assert ENTRY in RPLL
+    for key in sorted(KERNELS):
+        print(key, KERNELS[key])
+        assert "LockinAccu" in KERNELS[key], (key, KERNELS[key])

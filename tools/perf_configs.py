@@ -592,6 +592,62 @@ def rpll(lanes, frames, layout, iters, tag, chain_too=False, repeats=2):
             report(f"{tag}:lockin {name}", n, "sample", 12 * n, med, mn, repeat=r)
 
 
+def lockin_accu(lanes, frames, layout, iters, tag, repeats=2):
+    """idsp_lockin_i32_accu_process beside the chain it fuses, idsp_accu_lo_i32 -> idsp_lockin_i32_lo_process, on the same buffers
+    in one process: `frames` OUTPUT frames, k = 3 for the three low-pass shapes `rpll_chain` times and k = 0 once; the chain's two
+    entries also one by one, and idsp_lockin_i32_process (internal phase) at the same shape.  Bytes per sample: fused 12 + 8 / 2^k,
+    chain 36 + 8 / 2^k."""
+    lm = "LM" if layout else "FM"
+    n = lanes * frames
+    xs = torch.randint(-(1 << 28), 1 << 28, (n,), dtype=torch.int32, device=dev)
+    lo = torch.empty(n * 2, dtype=torch.int32, device=dev)
+    y = torch.empty(n * 2, dtype=torch.int32, device=dev)
+    kk = math.pi * (1 << 31) * 1e-3
+    step = torch.randint(-(1 << 31), (1 << 31) - 1, (lanes,), dtype=torch.int64, device=dev).to(torch.int32)
+    for (order, cascade), k in (((1, 1), 3), ((2, 1), 3), ((2, 2), 3), ((2, 2), 0)):
+        updates = frames >> k
+        accu = torch.randint(-(1 << 31), (1 << 31) - 1, (updates * lanes * 2,), dtype=torch.int64, device=dev).to(torch.int32)
+        lc = _abi.AccuLo(k, 1, 0)
+        lcfg = _abi.LockinI32()
+        lcfg.order, lcfg.cascade = order, cascade
+        for c in range(cascade):
+            if order == 1:
+                lcfg.k[c][0] = int(kk)
+            else:
+                lcfg.k[c][0], lcfg.k[c][1] = int(kk * kk / (1 << 32)), -int(kk * math.sqrt(2.0))
+        arm_words = call("lockin_state_words", C.byref(lcfg)) - 2
+        ast = torch.zeros((arm_words, lanes), dtype=torch.int32, device=dev)
+        lst = torch.zeros((2 + arm_words, lanes), dtype=torch.int32, device=dev)
+        lst[1] = step
+
+        def accu_lo():
+            call("accu_lo_i32", C.byref(lc), p(accu), p(lo), lanes, updates, layout, sptr())
+
+        def lockin_lo():
+            call("lockin_i32_lo_process", C.byref(lcfg), p(ast), p(xs), p(lo), p(y), lanes, frames, layout, sptr())
+
+        def chain():
+            accu_lo()
+            lockin_lo()
+
+        def fused():
+            call("lockin_i32_accu_process", C.byref(lcfg), C.byref(lc), p(ast), p(xs), p(accu), p(y), lanes, updates, layout, sptr())
+
+        name = f"Lowpass<{order}>x{cascade} k={k} {lm} {lanes}x{frames}"
+        for r in range(repeats):
+            med, mn = timeit(fused, iters)
+            report(f"{tag}:lockin_accu {name}", n, "sample", 12 * n + 8 * updates * lanes, med, mn, repeat=r, dispatch=call("last_kernel").decode())
+            med, mn = timeit(chain, iters)
+            report(f"{tag}:accu_lo + lockin_lo {name}", n, "sample", 36 * n + 8 * updates * lanes, med, mn, repeat=r, dispatch=call("last_kernel").decode())
+            med, mn = timeit(accu_lo, iters)
+            report(f"{tag}:accu_lo {name}", n, "sample", 8 * n + 8 * updates * lanes, med, mn, repeat=r)
+            med, mn = timeit(lockin_lo, iters)
+            report(f"{tag}:lockin_lo {name}", n, "sample", 20 * n, med, mn, repeat=r)
+            med, mn = timeit(lambda: call("lockin_i32_process", C.byref(lcfg), p(lst), p(xs), p(y), lanes, frames, layout, sptr()), iters)
+            report(f"{tag}:lockin {name}", n, "sample", 12 * n, med, mn, repeat=r, dispatch=call("last_kernel").decode())
+        del accu
+
+
 def copy_ref(nbytes, iters):
     a = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     b = torch.empty_like(a)
@@ -775,6 +831,12 @@ def main():
     for layout in (FM, LM):
         if want("rpll") or (sel is not None and f"rpll_chain_{'lm' if layout else 'fm'}" in sel):
             rpll(32768, 4096, layout, it, "rpll_chain", chain_too=True)
+    # the lock-in on `Accu` rows beside accu_lo -> lockin_lo at 65536, 32768 and 16384 lanes x 4096 in both layouts (`lockin_accu`, or one shape
+    # per process: lockin_accu_65536_fm, ... lockin_accu_16384_lm)
+    for lanes in (65536, 32768, 16384):
+        for layout in (FM, LM):
+            if want("lockin_accu") or (sel is not None and f"lockin_accu_{lanes}_{'lm' if layout else 'fm'}" in sel):
+                lockin_accu(lanes, 4096, layout, it, "lockin_accu")
     if want("cordic"):  # the CORDIC family at 2^26 elements with and without z, beside a copy of the same bytes and atan2 at the same n
         cordic(1 << 26, it, "cordic")
     if want("lockinc"):  # `Lockin<C>` with biquad arms at the C4 shape (thread-per-lane stream kernels)
