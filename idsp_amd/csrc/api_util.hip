@@ -52,7 +52,6 @@ void note_kernel_also(const char *also)
     LastKernel &k = last_kernel();
     k.also[k.also[0] ? 1 : 0] = also;
 }
-const char *noted_kernel() { return last_kernel().kernel; }
 
 namespace {
 

@@ -1,7 +1,8 @@
 // dispatch_thresholds.h — every lane-count / frame-count threshold the launchers of the lane-streaming families branch on, in ONE place
 // (round 5; VERDICT round 4, "upkeep").  Each was measured on MI355X boxes that differ by 3-5 %, so none of them is sharp; the file each
 // comes from is named, profiles/NOTES.md has the numbers, and tests/test_gpu_dispatch_table.py pins the kernel taken at every BASELINE
-// shape and on both sides of every cliff listed here.
+// shape and on both sides of every cliff listed here; tests/test_stream_plan.py pins the same table and both sides of every threshold without
+// a GPU, through `plan_stream` (stream_plan.h), which is the one reader of what follows.
 #pragma once
 
 #include <cstddef>
@@ -37,9 +38,29 @@ constexpr size_t kLdsMinWaves = 256;
 // two-wave chain kernel (stream_frame_major_duo): from this many lanes, chains of 5+ sections (4 sections up to kDuo4MaxLanes)
 constexpr size_t kDuoMinLanes = 40960, kDuo4MaxLanes = 98304;
 
+// a processor is "heavy" (VALU-bound: half-empty waves cost arithmetic) above this COST estimate; also the default LDS-DMA eligibility
+constexpr int kHeavyCost = 120;
+// one to three lanes in all on stream_frame_major_few, from this many frames (a tile is 256)
+constexpr size_t kFewMaxLanes = 3, kFewMinFrames = 64;
+// "lanes % 4 on a second stream": bodies from this many lanes, calls from this many frames
+constexpr size_t kOddSplitMinBody = 8192, kOddSplitMinFrames = 16;
+// "whole rounds + remainder": from this many frames; whole rounds on the sweep kernel only as a power of two up to this many rounds of 65536 lanes
+constexpr size_t kRoundsSplitMinFrames = 16, kRoundsSplitMaxRounds = 16;
+// staged single-wave kernel: from this many frames; XCD-contiguous lane blocks on rows off the 64-byte grid from this many workgroups
+constexpr size_t kStagedMinFrames = 16, kStagedXcdcMinGrid = 64;
+// sweep kernel: XCD-contiguous block order from this many workgroups; several frames per segment up to this many lanes per block
+constexpr size_t kSweepXcdcMinGrid = 8, kSweepFpsMaxBlockLanes = 128;
+// round-3 LDS-DMA kernel: several lanes per thread only when that leaves this many workgroups
+constexpr size_t kLdsLptMinGrid = 224, kLdsLptMaxGrid = 320;
+// register-window kernel: 256-thread workgroups from this many waves (below: one wave per workgroup, to reach all 256 CUs), the deep
+// prefetch window up to this many waves, XCD-contiguous blocks (a diagnostic switch) from this many workgroups
+constexpr size_t kWindowBlockMinWaves = 1024, kWindowDeepMaxWaves = 2048, kWindowXcdcMinGrid = 64;
+
 // ---- LaneMajor (launch_stream) -----------------------------------------------------------------------------------------------------
 // staged kernel, lanes per wave: 64 from here, 32 from here (or COST > 120), else 16
 constexpr size_t kLmStaged64Lanes = 49152, kLmStaged32Lanes = 24576;
+// ... from this many bytes per row on the wider side (a quarter of the staged kernel's 512-byte run: below, the tile kernel has less to set up)
+constexpr size_t kLmStagedMinRowBytes = 128;
 
 // ---- start-up stagger of the line-wise LaneMajor kernels (lockin_waves.h, dds.hip; MI355X in SPX mode only: stagger_tuned_device()) --
 constexpr unsigned kStaggerMinWorkgroups = 512;                     // launches of at least two workgroups per CU

@@ -67,39 +67,7 @@ struct SweepBigTwoBarrierOf : std::false_type {};
 template <class P>
 struct SweepBigTwoBarrierOf<P, std::void_t<decltype(P::SWEEP_BIG_TWO_BARRIER)>> : std::integral_constant<bool, P::SWEEP_BIG_TWO_BARRIER> {};
 
-struct SweepGeom {
-    int lpt = 1;             // sub-blocks per workgroup
-    unsigned grid = 0;       // workgroups
-    unsigned bw = 256;       // lanes per sub-block (multiple of 16, <= 256)
-    unsigned rounds = 1;     // sweeps inside the launch
-    unsigned fps = 1;        // frames per one-KiB segment (LPT = 1 and bw <= 128: launch_sweep sets it for 4-byte outputs)
-    size_t round_lanes = 0;  // lanes per sweep (the last one may hold fewer)
-};
-
-// Geometry for `lanes` lanes (a multiple of 4) with at most `max_lpt` sub-blocks per workgroup; false: not coverable
-// (fewer than 16 lanes).  Waste (lanes of capacity beyond the last lane) costs duplicate traffic of at most one
-// workgroup; a grid below 256 leaves CUs idle — scored 4 : 1 (tools/exp_fm_sweep.hip sweeps the alternatives).
-inline bool sweep_geometry(size_t lanes, int max_lpt, SweepGeom &out, unsigned max_grid = 256)
-{
-    if (lanes < 16 || max_lpt < 1) return false;
-    const size_t cap = size_t(max_grid) * size_t(max_lpt) * 256;
-    const size_t rounds = (lanes + cap - 1) / cap;
-    size_t lr = (lanes + rounds - 1) / rounds;
-    lr = (lr + 15) / 16 * 16;
-    int lpt = 1;
-    while (lpt < max_lpt && size_t(max_grid) * size_t(lpt) * 256 < lr) lpt *= 2;
-    double best = 1e30;
-    for (unsigned bw = 256; bw >= 16; bw -= 16) {
-        const size_t per = size_t(lpt) * bw, g = (lr + per - 1) / per;
-        if (g > max_grid) continue;
-        const double waste = double(g * per - lr) / double(lr), idle = double(max_grid - g) / double(max_grid);
-        const double score = waste + 0.25 * idle + (256 - bw) * 1e-5;
-        if (score < best) best = score, out.bw = bw, out.grid = unsigned(g);
-    }
-    if (best >= 1e30) return false;
-    out.lpt = lpt, out.rounds = unsigned(rounds), out.round_lanes = lr;
-    return true;
-}
+// (SweepGeom and sweep_geometry: stream_plan.h)
 
 template <class P>
 constexpr size_t sweep_lds_bytes(int nb = kSweepNB, int ts = kSweepT)
@@ -480,7 +448,7 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major_sweep(
 // ------------------------------------------------------------------------------------------------------------ host
 // Largest LPT a processor is instantiated with (each doubling doubles its state registers, the unrolled loop body and the build time): the
 // single biquad sections (P::SWEEP_MAX_LPT = 16) take every lane count up to 2^20 in ONE sweep; `Normal`, the per-lane banks and two-section chains
-// (8) up to 524288, and 2^20 as two sweeps over half rows; everything else (4, heavy bodies 2) one sweep only — `sweep_takes` below.
+// (8) up to 524288, and 2^20 as two sweeps over half rows; everything else (4, heavy bodies 2) one sweep only — `sweep_takes` (stream_plan.h).
 template <class P, class = void>
 struct SweepMaxLptOf {
     static constexpr int value = P::COST <= 120 ? 4 : 2;  // (single biquad sections declare 16: biquad_sections.h)
@@ -489,10 +457,9 @@ template <class P>
 struct SweepMaxLptOf<P, std::void_t<decltype(P::SWEEP_MAX_LPT)>> {
     static constexpr int value = P::SWEEP_MAX_LPT;
 };
-// smallest lane count the sweep kernel takes: 49152, or 24576 for 4-byte outputs, where several frames share a segment (`fps`: 32768 lanes 0.69 of
+// (smallest lane count the sweep kernel takes, thr::kSweepMinLanes / kSweepMinLanesFps: 49152, or 24576 for 4-byte outputs, where several frames share a segment (`fps`: 32768 lanes 0.69 of
 // the HBM peak against 0.56 on the staged single-wave kernel, 24576 0.52 against 0.50; at 16384 lanes the staged kernel's 36 ns per frame win, 0.46
-// against 0.42 — a `v_mad_i64_i32` occupies its SIMD for 16 cycles per 64-lane wave, five per step: 80 cycles x 4096 steps = 0.137 ms whatever the schedule)
-constexpr size_t kSweepMinLanes = thr::kSweepMinLanes, kSweepMinLanesFps = thr::kSweepMinLanesFps;
+// against 0.42 — a `v_mad_i64_i32` occupies its SIMD for 16 cycles per 64-lane wave, five per step: 80 cycles x 4096 steps = 0.137 ms whatever the schedule.)
 
 template <class P, int LPT>
 int launch_sweep_lpt(const typename P::Params &prm, uint32_t *st, const typename P::In *x, typename P::Out *y, size_t lanes, size_t frames, size_t xl,
@@ -559,72 +526,29 @@ int launch_sweep_lpt(const typename P::Params &prm, uint32_t *st, const typename
     return launch_status();
 }
 
-// Whether the sweep kernel is the one to take for `lanes` lanes of P: when the launch is ONE sweep, or when its sweeps are at least 8 blocks per
-// workgroup wide (2 MiB of every row).  Several narrower sweeps per launch are the panel walk again (rows at a stride, 1 MiB or less of each): 2^20 lanes
-// in four sweeps of 4 blocks per workgroup 0.54-0.57 of the HBM peak for every family against 0.60-0.62 on round 4's dispatch, which those launches keep
-// (profiles/r05_perf_big_lanes.txt).
+// The launch of a plan of form FmSweep (stream_plan.h: geometry, frames per segment, block order and the name are the plan's; `lanes` is a multiple
+// of 4: whole 16-byte pieces; rows need dword alignment only, and off the 64-byte grid the blocks go to the XCDs in contiguous eighths).
 template <class P>
-bool sweep_takes(size_t lanes)
+int launch_sweep(const typename P::Params &prm, uint32_t *st, const typename P::In *x, typename P::Out *y, size_t lanes, size_t frames, size_t sp,
+                 const StreamPlan &p, hipStream_t s)
 {
-    SweepGeom g;
-    static const unsigned max_grid = unsigned(diag_size("IDSP_SWEEP_MAX_GRID", 256));
-    if (!sweep_geometry(lanes, SweepMaxLptOf<P>::value, g, max_grid ? max_grid : 256u)) return false;
-    return g.rounds == 1 || g.lpt >= thr::kSweepMinLptSeveralSweeps || max_grid != 256;  // (a capped grid is the tests' way to reach several sweeps per launch at small sizes)
-}
-
-// The launch for `lanes` lanes (a multiple of 4: whole 16-byte pieces; rows need dword alignment only — `global_load_lds_dwordx4` and the
-// 16-byte stores take it, round 3 — and off the 64-byte grid the blocks go to the XCDs in contiguous eighths).  Returns IDSP_OK or an error.
-template <class P>
-int launch_sweep(const typename P::Params &prm, uint32_t *st, const typename P::In *x, typename P::Out *y, size_t lanes, size_t frames, size_t xl, size_t yl,
-                 size_t sp, hipStream_t s)
-{
-    const bool on_grid64 = reinterpret_cast<uintptr_t>(x) % 64 == 0 && reinterpret_cast<uintptr_t>(y) % 64 == 0 && (xl * sizeof(typename P::In)) % 64 == 0 &&
-                           (yl * sizeof(typename P::Out)) % 64 == 0;
-    static const bool no_xcdc = diag_env("IDSP_SWEEP_NO_XCDC") != nullptr;
-    static const bool force_xcdc = diag_env("IDSP_SWEEP_FORCE_XCDC") != nullptr;  // IDSP_DIAG=1: the XCD-contiguous block order on every launch
-    const unsigned xcdc = (!on_grid64 && !no_xcdc) || force_xcdc ? 1u : 0u;
     constexpr int kMax = SweepMaxLptOf<P>::value;
-    SweepGeom g;
-    // (IDSP_DIAG=1 IDSP_SWEEP_MAX_GRID=n: at most n workgroups — small tensors then reach every LPT and several sweeps per launch: tests)
-    static const unsigned max_grid = unsigned(diag_size("IDSP_SWEEP_MAX_GRID", 256));
-    if (!sweep_geometry(lanes, kMax, g, max_grid ? max_grid : 256u)) return fail(IDSP_EINVAL, "internal: no sweep geometry for %zu lanes", lanes);
-    // few lanes per workgroup (below 32768 + lanes in all): several frames per one-KiB segment, so that a tile stays 8 KiB of real samples
-    // (IDSP_DIAG=1 IDSP_SWEEP_NO_FPS=1: one frame per segment)
-    static const bool no_fps = diag_env("IDSP_SWEEP_NO_FPS") != nullptr;
-    const bool fps_form = g.lpt == 1 && sizeof(typename P::Out) == 4 && g.bw <= 128 && !no_fps;
-    if (fps_form) {
-        unsigned f = 256u / g.bw;
-        while (f > 1 && (size_t(f - 1) * kSweepT * (xl > yl ? xl : yl) + 256) * 4 >= (size_t(1) << 32)) f--;  // per-thread byte offsets are 32-bit
-        g.fps = f;
-    }
-    static const char *const names[] = {"stream_frame_major_sweep[1 block/workgroup]", "stream_frame_major_sweep[2 blocks/workgroup]",
-                                        "stream_frame_major_sweep[4 blocks/workgroup]", "stream_frame_major_sweep[8 blocks/workgroup]",
-                                        "stream_frame_major_sweep[16 blocks/workgroup]"};
-    int k = 0;
-    while ((1 << k) < g.lpt) k++;
-    static const char *const names_x[] = {"stream_frame_major_sweep[1 block/workgroup, XCD-contiguous]", "stream_frame_major_sweep[2 blocks/workgroup, XCD-contiguous]",
-                                          "stream_frame_major_sweep[4 blocks/workgroup, XCD-contiguous]", "stream_frame_major_sweep[8 blocks/workgroup, XCD-contiguous]",
-                                          "stream_frame_major_sweep[16 blocks/workgroup, XCD-contiguous]"};
-    note_kernel(xcdc && g.grid >= 8 ? names_x[k] : names[k], typeid(P).name());
-    if (fps_form) {
-        // the frames per segment, 1 where the 32-bit guard above brought them down (tests pin both sides of it)
-        static thread_local char fps_text[32];
-        snprintf(fps_text, sizeof(fps_text), " [%u frame%s/segment]", g.fps, g.fps == 1 ? "" : "s");
-        note_kernel_also(fps_text);
-    }
+    const SweepGeom &g = p.geom;
+    note_kernel(stream_plan_name(p), typeid(P).name());
+    if (const char *also = stream_plan_also(p)) note_kernel_also(also);
     if constexpr (kMax >= 16) {
-        if (g.lpt == 16) return launch_sweep_lpt<P, 16>(prm, st, x, y, lanes, frames, xl, yl, sp, g, s, xcdc && g.grid >= 8);
+        if (g.lpt == 16) return launch_sweep_lpt<P, 16>(prm, st, x, y, lanes, frames, p.xl, p.yl, sp, g, s, p.xcdc);
     }
     if constexpr (kMax >= 8) {
-        if (g.lpt == 8) return launch_sweep_lpt<P, 8>(prm, st, x, y, lanes, frames, xl, yl, sp, g, s, xcdc && g.grid >= 8);
+        if (g.lpt == 8) return launch_sweep_lpt<P, 8>(prm, st, x, y, lanes, frames, p.xl, p.yl, sp, g, s, p.xcdc);
     }
     if constexpr (kMax >= 4) {
-        if (g.lpt == 4) return launch_sweep_lpt<P, 4>(prm, st, x, y, lanes, frames, xl, yl, sp, g, s, xcdc && g.grid >= 8);
+        if (g.lpt == 4) return launch_sweep_lpt<P, 4>(prm, st, x, y, lanes, frames, p.xl, p.yl, sp, g, s, p.xcdc);
     }
     if constexpr (kMax >= 2) {
-        if (g.lpt == 2) return launch_sweep_lpt<P, 2>(prm, st, x, y, lanes, frames, xl, yl, sp, g, s, xcdc && g.grid >= 8);
+        if (g.lpt == 2) return launch_sweep_lpt<P, 2>(prm, st, x, y, lanes, frames, p.xl, p.yl, sp, g, s, p.xcdc);
     }
-    return launch_sweep_lpt<P, 1>(prm, st, x, y, lanes, frames, xl, yl, sp, g, s, xcdc && g.grid >= 8);
+    return launch_sweep_lpt<P, 1>(prm, st, x, y, lanes, frames, p.xl, p.yl, sp, g, s, p.xcdc);
 }
 
 }  // namespace idsp

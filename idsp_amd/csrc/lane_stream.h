@@ -1575,19 +1575,32 @@ inline size_t diag_size(const char *name, size_t dflt)
 }
 
 }  // namespace idsp
-#include "fm_sweep.h"  // the dense-sweep FrameMajor kernel (round 5): needs everything above, is needed by launch_stream below
+#include "stream_plan.h"  // which kernel a call takes: the pure half of the launcher below
+#include "fm_sweep.h"     // the dense-sweep FrameMajor kernel (round 5): needs everything above, is needed by launch_stream below
 namespace idsp {
 
 // --------------------------------------------------------------------- launch
-// Prefetch depth by occupancy: at <= 2 waves/SIMD nothing else hides HBM
-// latency, so go deep; with many resident waves keep the register budget low.
-// smallest launch (in waves) that takes the 256-thread LDS-DMA kernel (IDSP_DIAG=1 IDSP_LDS_MIN_WAVES overrides):
-// measured equal to the single-wave register kernel at 16384 lanes, 15-20 % ahead at 32768-49152,
-// slightly behind at 8192
-inline size_t lds_min_waves()
+static_assert(kPlanWave == size_t(kWave) && kPlanBlock == size_t(kFmBlock) && kPlanSweepSegments == size_t(kSweepT) &&
+                  thr::kLmStagedMinRowBytes == size_t(kLmRun) / 4 && thr::kLdsGridCap == kLdsGridCap,
+              "stream_plan.h restates these");
+
+// The kernel-selection switches of launch_stream and duo_wanted, read once per process (honoured only with IDSP_DIAG=1: diag_env)
+inline const StreamSwitches &stream_switches()
 {
-    static const size_t v = diag_size("IDSP_LDS_MIN_WAVES", thr::kLdsMinWaves);
-    return v;
+    static const StreamSwitches sw = read_stream_switches(diag_env);
+    return sw;
+}
+
+// What plan_stream reads from a processor
+template <class P>
+constexpr StreamTraits traits_of()
+{
+    StreamTraits t;
+    t.has_in = P::HAS_IN, t.in_div = P::IN_DIV, t.in_bytes = sizeof(typename P::In), t.out_bytes = sizeof(typename P::Out), t.cost = P::COST;
+    t.lds_eligible = LdsEligibleOf<P>::value, t.lds_lpt_max = LdsLptMaxOf<P>::value, t.lds_ring = LdsRingOf<P>::value;
+    t.fm_staged = FmStagedOf<P>::value, t.lm_staged = LmStagedOf<P>::value, t.lm_one_form = LmOneFormOf<P>::value;
+    t.sweep_max_lpt = SweepMaxLptOf<P>::value;
+    return t;
 }
 
 // Row pitches of a call: elements between consecutive frames (FRAME_MAJOR) or between the starts of consecutive
@@ -1616,16 +1629,211 @@ inline Params shift_lanes(Params p, size_t first, size_t elem)
     return p;
 }
 
-// Largest remainder (in lanes) that launch_stream runs beside the whole rounds on a second stream (tools/exp_split_streams.py:
-// 73728 lanes 0.58 -> 0.69 of the HBM peak with an 8192-lane remainder, 81920 0.59 -> 0.63 with 16384, no gain from 24576 up)
-constexpr size_t kSplitTailMax = thr::kSplitTailMax;
+// One call as the per-form launch functions below see it (`sp`: lanes between the state planes)
+template <class P>
+struct StreamArgs {
+    const typename P::Params &prm;
+    uint32_t *st;
+    const typename P::In *x;
+    typename P::Out *y;
+    size_t lanes, frames, sp;
+    hipStream_t s;
+};
 
-// set while launch_stream launches the remainder of a "whole rounds + remainder" split on the second stream: that launch keeps the staged kernel
-// (beside the sweep kernel's whole rounds the pair kernel's remainder costs 6-10 %: 69632 lanes 0.413 -> 0.454 ms, profiles/r06_exp_fm_pair.txt)
-inline bool &split_remainder_flag()
+// One function per form of the plan: each notes the name stream_plan_name gives the plan and launches that kernel.  The `if constexpr` /
+// `static_assert` conditions are those under which launch_call reaches them: a processor instantiates exactly the kernels it can take.
+template <class P>
+int launch_lm_tile(const StreamArgs<P> &a, const StreamPlan &p)
 {
-    static thread_local bool f = false;
-    return f;
+    note_kernel(stream_plan_name(p), typeid(P).name());
+    hipLaunchKernelGGL((stream_lane_major<P>), dim3(p.grid), dim3(kWave), 0, a.s, a.prm, a.st, a.x, a.y, a.lanes, a.frames, p.xl, p.yl);
+    return launch_status();
+}
+
+template <class P>
+int launch_lm_staged(const StreamArgs<P> &a, const StreamPlan &p)
+{
+    auto go = [&](auto lw_tag) {
+        constexpr int LW = decltype(lw_tag)::value;
+        // the 32- and 16-lane forms move 1 KiB per lane and tile (the same 32 / 16 KiB slot and staging registers
+        // as 512-byte runs would need at twice the lanes): 5-10 % faster at 16384 lanes and below, 10-20 % on rows
+        // that are not 128-byte aligned, equal at 65536 lanes (profiles/r02_tune_lm_run1k.jsonl)
+        constexpr int LB = LW == 64 ? kLmRun : 2 * kLmRun;
+        constexpr size_t bytes = lm_staged_lds_bytes<P, LW, LB>();
+        if (int rc = ensure_dyn_lds<&stream_lane_major_staged<P, LW, LB>>(bytes)) return rc;
+        note_kernel(stream_plan_name(p), typeid(P).name());
+        const StreamSwitches &sw = stream_switches();
+        const unsigned lm_skew = unsigned(sw.lm_skew), lm_skew_shift = (unsigned(sw.lm_skew_shift) & 31u) | ((unsigned(sw.lm_skew_mod) & 255u) << 8);
+        hipLaunchKernelGGL((stream_lane_major_staged<P, LW, LB>), dim3(p.grid), dim3(kWave), bytes, a.s, a.prm, a.st, a.x, a.y, a.lanes, a.frames, p.xl, p.yl,
+                           lm_skew, lm_skew_shift);
+        return launch_status();
+    };
+    // forms instantiated per processor: all three for the cheap ones, 64 / 32 for the heavy ones, 64 only for P::LM_ONE_FORM (plan_lane_major)
+    if constexpr (!LmOneFormOf<P>::value) {
+        if constexpr (!traits_of<P>().heavy()) {
+            if (p.lanes_per_wave == 16) return go(std::integral_constant<int, 16>{});
+        }
+        if (p.lanes_per_wave == 32) return go(std::integral_constant<int, 32>{});
+    }
+    return go(std::integral_constant<int, 64>{});
+}
+
+// n = 1 ... 3 lanes from lane `first` of the call, on stream `s`
+template <class P>
+int launch_fm_few(const StreamArgs<P> &a, const StreamPlan &p, size_t first, size_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL((stream_frame_major_few<P>), dim3(1), dim3(kWave), 0, s, shift_lanes(a.prm, first, sizeof(typename P::In)), a.st + first, a.x + first,
+                       a.y + first, int(n), a.frames, p.xl, p.yl, a.sp);
+    return launch_status();
+}
+
+template <class P>
+int launch_fm_pair(const StreamArgs<P> &a, const StreamPlan &p)
+{
+    constexpr size_t bytes = 2 * size_t(kFmPairTile) + size_t(P::LDS_WORDS) * 4;
+    if (int rc = ensure_dyn_lds<&stream_frame_major_pair<P>>(bytes)) return rc;
+    note_kernel(stream_plan_name(p), typeid(P).name());
+    hipLaunchKernelGGL((stream_frame_major_pair<P>), dim3(unsigned((a.lanes + 31) / 32)), dim3(2 * kWave), bytes, a.s, a.prm, a.st, a.x, a.y, a.lanes, a.frames,
+                       p.xl, p.yl, a.sp);
+    return launch_status();
+}
+
+template <class P>
+int launch_fm_staged(const StreamArgs<P> &a, const StreamPlan &p)
+{
+    auto go = [&](auto lw_tag) {
+        constexpr int LW = decltype(lw_tag)::value;
+        constexpr size_t bytes = size_t(kFmStagedTile) + size_t(P::LDS_WORDS) * 4;
+        if (int rc = ensure_dyn_lds<&stream_frame_major_staged<P, LW>>(bytes)) return rc;
+        note_kernel(stream_plan_name(p), typeid(P).name());
+        hipLaunchKernelGGL((stream_frame_major_staged<P, LW>), dim3(p.grid), dim3(kWave), bytes, a.s, a.prm, a.st, a.x, a.y, a.lanes, a.frames, p.xl, p.yl, a.sp,
+                           p.staged_flags);
+        return launch_status();
+    };
+    if constexpr (!traits_of<P>().heavy()) {
+        if (p.lanes_per_wave == 16) return go(std::integral_constant<int, 16>{});
+        if (p.lanes_per_wave == 64) return go(std::integral_constant<int, 64>{});
+    }
+    return go(std::integral_constant<int, 32>{});
+}
+
+template <class P>
+int launch_fm_lds(const StreamArgs<P> &a, const StreamPlan &p)
+{
+    constexpr size_t ow = sizeof(typename P::Out) / 4;
+    constexpr int kMaxLpt = LdsLptMaxOf<P>::value;
+    auto go = [&](auto lpt_tag, auto deep, auto xcdc) {
+        constexpr int L = decltype(lpt_tag)::value;
+        constexpr bool DEEP = decltype(deep)::value, XCDC = decltype(xcdc)::value;
+        constexpr int NB = DEEP ? 7 : LdsRingOf<P>::value;
+        constexpr bool RUN = DEEP ? false : LdsRunOf<P>::value;
+        constexpr size_t ts = L > kLdsT ? L : kLdsT;
+        constexpr size_t bytes = (size_t(NB) * ts * kFmBlock + 2 * ts * kFmBlock * ow + P::LDS_WORDS) * 4;
+        if (int rc = ensure_dyn_lds<&stream_frame_major_lds<P, NB, L, RUN, XCDC>>(bytes)) return rc;
+        note_kernel(stream_plan_name(p), typeid(P).name());
+        hipLaunchKernelGGL((stream_frame_major_lds<P, NB, L, RUN, XCDC>), dim3(p.grid), dim3(kFmBlock), bytes, a.s, a.prm, a.st, a.x, a.y, a.lanes, a.frames, p.xl,
+                           p.yl, a.sp);
+        return launch_status();
+    };
+    using Yes = std::true_type;
+    using No = std::false_type;
+    if constexpr (kMaxLpt >= 4) {
+        if (p.lanes_per_thread == 4) return go(std::integral_constant<int, 4>{}, No{}, No{});
+    }
+    if constexpr (kMaxLpt >= 2) {
+        if (p.lanes_per_thread == 2) return go(std::integral_constant<int, 2>{}, No{}, No{});
+    }
+    if (p.xcdc) return go(std::integral_constant<int, 1>{}, Yes{}, Yes{});  // XCD-contiguous blocks: always the deep ring
+    if (p.deep_ring) return go(std::integral_constant<int, 1>{}, Yes{}, No{});
+    return go(std::integral_constant<int, 1>{}, No{}, No{});
+}
+
+template <class P>
+int launch_fm_window(const StreamArgs<P> &a, const StreamPlan &p)
+{
+    constexpr int kDeep = MaxU<P>::value, kShallow = kDeep < 8 ? kDeep : 8;
+    note_kernel(stream_plan_name(p), typeid(P).name());
+    if (p.deep_window)
+        hipLaunchKernelGGL((stream_frame_major<P, kDeep>), dim3(p.grid), dim3(p.block), 0, a.s, a.prm, a.st, a.x, a.y, a.lanes, a.frames, p.xl, p.yl, int(p.xcdc), a.sp);
+    else
+        hipLaunchKernelGGL((stream_frame_major<P, kShallow>), dim3(p.grid), dim3(p.block), 0, a.s, a.prm, a.st, a.x, a.y, a.lanes, a.frames, p.xl, p.yl, int(p.xcdc), a.sp);
+    return launch_status();
+}
+
+// Plans the call `c` (x and y are its two addresses, typed) and launches what the plan says; `took`: the form it took
+template <class P>
+int launch_call(const typename P::Params &prm, uint32_t *st, const typename P::In *x, typename P::Out *y, StreamCall c, hipStream_t s, StreamForm *took = nullptr)
+{
+    constexpr StreamTraits t = traits_of<P>();
+    const size_t sp = c.state_pitch ? c.state_pitch : c.lanes;  // lanes between the state planes (a lane block of a larger call keeps the call's)
+    if (c.layout == IDSP_LANE_MAJOR && sp != c.lanes) return fail(IDSP_EINVAL, "internal: lane block with a state pitch on a LaneMajor kernel");
+    StreamPlan p = plan_stream(t, c, stream_switches());
+    SideStream *ss = nullptr;
+    if (p.form == StreamForm::FmOddBeside || p.form == StreamForm::FmRoundsBeside) {
+        // a caller whose stream lives on another device than the current one has no second stream: the unsplit forms
+        if (!(ss = side_stream(s))) c.no_side_stream = true, p = plan_stream(t, c, stream_switches());
+    }
+    if (took) *took = p.form;
+    const StreamArgs<P> a{prm, st, x, y, c.lanes, c.frames, sp, s};
+    switch (p.form) {
+        case StreamForm::LmTile: return launch_lm_tile<P>(a, p);
+        case StreamForm::LmStaged:
+            if constexpr (t.lm_staged) return launch_lm_staged<P>(a, p);
+            break;
+        case StreamForm::FmFew:
+            if constexpr (t.four_four()) {
+                note_kernel(stream_plan_name(p), typeid(P).name());
+                return launch_fm_few<P>(a, p, 0, c.lanes, s);
+            }
+            break;
+        case StreamForm::FmOddBeside:
+            // the last lanes % 4 on the second stream, the body (a lane block of the caller's tensors) on the caller's
+            if constexpr (t.four_four()) {
+                IDSP_HIP_TRY(hipEventRecord(ss->fork, s));
+                IDSP_HIP_TRY(hipStreamWaitEvent(ss->stream, ss->fork, 0));
+                int rc = launch_fm_few<P>(a, p, p.body, p.odd, ss->stream);
+                if (rc == IDSP_OK) rc = launch_call<P>(prm, st, x, y, lane_block(c, p, 0, p.body, false), s);
+                IDSP_HIP_TRY(hipEventRecord(ss->join, ss->stream));
+                IDSP_HIP_TRY(hipStreamWaitEvent(s, ss->join, 0));
+                if (rc == IDSP_OK) note_kernel_also(stream_plan_also(p));
+                return rc;
+            }
+            break;
+        case StreamForm::FmRoundsBeside:
+            // the whole rounds on the caller's stream, the remainder beside them on the second: both are lane blocks of the caller's
+            // tensors (row pitches xl / yl, state and coefficient planes at the call's pitch)
+            if constexpr (t.fm_staged && t.four_four() && !t.heavy()) {
+                IDSP_HIP_TRY(hipEventRecord(ss->fork, s));
+                IDSP_HIP_TRY(hipStreamWaitEvent(ss->stream, ss->fork, 0));
+                // which kernel the whole rounds go to: the dense-sweep kernel, or the LDS-DMA panel walk for the processors / shapes the sweep does not take
+                StreamForm head_form = StreamForm::FmLds;
+                int rc = launch_call<P>(prm, st, x, y, lane_block(c, p, 0, p.head, false), s, &head_form);
+                p.head_swept = head_form == StreamForm::FmSweep;
+                if (rc == IDSP_OK)
+                    rc = launch_call<P>(shift_lanes(prm, p.head, sizeof(typename P::In)), st + p.head, x + p.head, y + p.head, lane_block(c, p, p.head, p.tail, true),
+                                        ss->stream);
+                // join even after a failed launch: the caller's stream must not run ahead of whatever the side stream holds
+                IDSP_HIP_TRY(hipEventRecord(ss->join, ss->stream));
+                IDSP_HIP_TRY(hipStreamWaitEvent(s, ss->join, 0));
+                if (rc == IDSP_OK) note_kernel(stream_plan_name(p), typeid(P).name());
+                return rc;
+            }
+            break;
+        case StreamForm::FmPair:
+            if constexpr (t.fm_staged && t.four_four() && t.cost <= thr::kPairMaxCost) return launch_fm_pair<P>(a, p);
+            break;
+        case StreamForm::FmSweep:
+            if constexpr (t.lds_input() && t.lds_eligible) return launch_sweep<P>(prm, st, x, y, c.lanes, c.frames, sp, p, s);
+            break;
+        case StreamForm::FmStaged:
+            if constexpr (t.fm_staged) return launch_fm_staged<P>(a, p);
+            break;
+        case StreamForm::FmLds:
+            if constexpr (t.lds_input()) return launch_fm_lds<P>(a, p);
+            break;
+        case StreamForm::FmWindow: return launch_fm_window<P>(a, p);
+    }
+    return fail(IDSP_EINVAL, "internal: the plan names a kernel this processor does not have");
 }
 
 template <class P>
@@ -1633,340 +1841,11 @@ int launch_stream(const typename P::Params &prm, void *state, const typename P::
                   typename P::Out *y, size_t lanes, size_t frames, int layout, hipStream_t s, Pitch pitch = {}, size_t state_pitch = 0)
 {
     if (lanes == 0) return IDSP_OK;
-    uint32_t *st = static_cast<uint32_t *>(state);
-    const size_t sp = state_pitch ? state_pitch : lanes;  // lanes between the state planes (a lane block of a larger call keeps the call's)
-    if (layout == IDSP_LANE_MAJOR) {
-        if (sp != lanes) return fail(IDSP_EINVAL, "internal: lane block with a state pitch on a LaneMajor kernel");
-        const size_t xl = pitch.x ? pitch.x : frames, yl = pitch.y ? pitch.y : frames;
-        const unsigned grid = unsigned((lanes + kWave - 1) / kWave);
-        if constexpr (LmStagedOf<P>::value) {
-            // 16-byte pieces need 16-byte aligned rows (of less than 64 MiB: 32-bit offsets inside a wave's 64 rows); below a
-            // quarter tile of frames the 4-byte tile kernel has less to set up
-            // (IDSP_DIAG=1 IDSP_NO_LM_STAGED=1: always the tile kernel)
-            static const bool no_staged = diag_env("IDSP_NO_LM_STAGED") != nullptr;
-            constexpr size_t isz = P::HAS_IN ? sizeof(typename P::In) : 0, osz = sizeof(typename P::Out), wide = isz > osz ? isz : osz;
-            const bool x_ok = !P::HAS_IN || (reinterpret_cast<uintptr_t>(x) % 16 == 0 && (xl * isz) % 16 == 0 && xl * isz < (size_t(1) << 26));
-            if (!no_staged && frames * wide >= size_t(kLmRun) / 4 && x_ok && reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
-                (yl * osz) % 16 == 0 && yl * osz < (size_t(1) << 26)) {
-                // lanes per wave: 64 when that already gives every SIMD a wave, else 32 or 16 (tools/tune_lm.hip;
-                // IDSP_DIAG=1 IDSP_LM_LANES_PER_WAVE = 64 / 32 / 16 forces one)
-                static const size_t forced_lw = diag_size("IDSP_LM_LANES_PER_WAVE", 0);
-                // measured (profiles/r02_tune_lm_lanes_per_wave.jsonl, 4096 frames): i32 DF1 at 16384 lanes 0.168 / 0.157 / 0.136 ms
-                // with 64 / 32 / 16 lanes per wave, at 32768 lanes 0.232 / 0.216 / 0.213, at 65536 0.382 / 0.393 / 0.446; the
-                // 8-section cascade (VALU-bound: half-empty waves cost arithmetic) 0.57 / 0.45 / 0.52 at 16384 and
-                // 0.61 / 0.91 / 1.56 at 65536
-                constexpr bool heavy = P::COST > 120;
-                const size_t lw = forced_lw ? forced_lw : lanes >= thr::kLmStaged64Lanes ? 64 : (lanes >= thr::kLmStaged32Lanes || heavy) ? 32 : 16;
-                auto go = [&](auto lw_tag) {
-                    constexpr int LW = decltype(lw_tag)::value;
-                    // the 32- and 16-lane forms move 1 KiB per lane and tile (the same 32 / 16 KiB slot and staging registers
-                    // as 512-byte runs would need at twice the lanes): 5-10 % faster at 16384 lanes and below, 10-20 % on rows
-                    // that are not 128-byte aligned, equal at 65536 lanes (profiles/r02_tune_lm_run1k.jsonl)
-                    constexpr int LB = LW == 64 ? kLmRun : 2 * kLmRun;
-                    constexpr size_t bytes = lm_staged_lds_bytes<P, LW, LB>();
-                    if (int rc = ensure_dyn_lds<&stream_lane_major_staged<P, LW, LB>>(bytes)) return rc;
-                    note_kernel(LW == 64 ? "stream_lane_major_staged" : LW == 32 ? "stream_lane_major_staged[32 lanes/wave]" : "stream_lane_major_staged[16 lanes/wave]",
-                                typeid(P).name());
-                    static const unsigned lm_skew = unsigned(diag_size("IDSP_LM_SKEW", 0)),
-                                          lm_skew_shift = (unsigned(diag_size("IDSP_LM_SKEW_SHIFT", 8)) & 31u) | ((unsigned(diag_size("IDSP_LM_SKEW_MOD", 2)) & 255u) << 8);
-                    hipLaunchKernelGGL((stream_lane_major_staged<P, LW, LB>), dim3(unsigned((lanes + LW - 1) / LW)), dim3(kWave), bytes, s, prm, st, x, y,
-                                       lanes, frames, xl, yl, lm_skew, lm_skew_shift);
-                    return launch_status();
-                };
-                // forms instantiated per processor: all three for the cheap ones, 64 / 32 for the heavy ones (never 16 above),
-                // 64 only for processors that ask for it (P::LM_ONE_FORM: rarely taken fall-back paths; build time)
-                if constexpr (!LmOneFormOf<P>::value) {
-                    if constexpr (!heavy) {
-                        if (lw == 16) return go(std::integral_constant<int, 16>{});
-                    }
-                    if (lw <= 32) return go(std::integral_constant<int, 32>{});
-                }
-                return go(std::integral_constant<int, 64>{});
-            }
-        }
-        note_kernel("stream_lane_major", typeid(P).name());
-        hipLaunchKernelGGL((stream_lane_major<P>), dim3(grid), dim3(kWave), 0, s, prm, st, x, y, lanes, frames, xl, yl);
-    } else {
-        const size_t xl = pitch.x ? pitch.x : lanes / P::IN_DIV, yl = pitch.y ? pitch.y : lanes;
-        const size_t waves = (lanes + kWave - 1) / kWave;
-        // Whole rounds + remainder (round 3).  The LDS-DMA kernel runs one 256-lane block per CU and round; 65540 lanes are 257
-        // blocks — one CU with two workgroups, both at half speed — and 73728 lanes 288: 0.58 of the HBM peak where 65536 run at
-        // 0.78.  The lanes beyond the last whole round of 256 blocks therefore run BESIDE the whole rounds, on a second stream,
-        // on the staged single-wave kernel (its waves spread over all CUs and fit next to the LDS-DMA workgroups): 69632 lanes
-        // 0.57 -> 0.65, 73728 0.58 -> 0.69, 81920 0.59 -> 0.63, 147456 0.59 -> 0.65; no gain from a 24576-lane remainder up
-        // (tools/exp_split_streams.py, profiles/r03_exp_split_streams.jsonl).  Both pieces are lane blocks of the caller's
-        // tensors (row pitches xl / yl, state and coefficient planes at the call's pitch).
-        // Rows that are only 4-byte aligned (round 3): a dense tensor of 65537 lanes, an odd pitch, a base pointer off the 16-byte grid.
-        // `global_load_lds_dwordx4`, `global_load_dwordx4` and the 16-byte stores only need dword alignment, so the LDS-DMA kernel
-        // and the staged kernel run on such rows as they are (tools/exp_fm_unaligned4.hip, profiles/r03_exp_fm_unaligned4.jsonl: bit for
-        // bit the register-window kernel's output; 65536 lanes at pitch 65537 0.65 of the HBM peak with XCD-contiguous blocks against 0.41
-        // for the register-window kernel's 4-byte accesses).  What they do need is whole 16-byte pieces per row, i.e. a lane count that
-        // is a multiple of 4: the last lanes % 4 lanes run beside the rest on the second stream (stream_frame_major_few).
-        // (IDSP_DIAG=1 IDSP_ALIGN16_ONLY=1: round 2's rule — 16-byte aligned rows or the register-window kernel)
-        static const bool align16_only = diag_env("IDSP_ALIGN16_ONLY") != nullptr;
-        const bool on_grid16 = reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0 && (xl * sizeof(typename P::In)) % 16 == 0 &&
-                               (yl * sizeof(typename P::Out)) % 16 == 0;
-        const bool rows_ok = on_grid16 || !align16_only;
-        if constexpr (P::HAS_IN && P::IN_DIV == 1 && sizeof(typename P::In) == 4 && sizeof(typename P::Out) == 4) {
-            static const bool no_few = diag_env("IDSP_NO_FM_FEW") != nullptr;
-            if (lanes <= 3 && frames >= 64 && !no_few) {  // one to three lanes in all: the same kernel, on the caller's stream
-                note_kernel("stream_frame_major_few", typeid(P).name());
-                hipLaunchKernelGGL((stream_frame_major_few<P>), dim3(1), dim3(kWave), 0, s, prm, st, x, y, int(lanes), frames, xl, yl, sp);
-                return launch_status();
-            }
-            const size_t odd = lanes % 4, body = lanes - odd;
-            if (odd && !align16_only && body >= 8192 && frames >= 16 && (FmStagedOf<P>::value || LdsEligibleOf<P>::value)) {
-                if (SideStream *ss = side_stream(s)) {
-                    IDSP_HIP_TRY(hipEventRecord(ss->fork, s));
-                    IDSP_HIP_TRY(hipStreamWaitEvent(ss->stream, ss->fork, 0));
-                    hipLaunchKernelGGL((stream_frame_major_few<P>), dim3(1), dim3(kWave), 0, ss->stream, shift_lanes(prm, body, sizeof(typename P::In)), st + body,
-                                       x + body, y + body, int(odd), frames, xl, yl, sp);
-                    int rc = launch_status();
-                    if (rc == IDSP_OK) rc = launch_stream<P>(prm, st, x, y, body, frames, layout, s, Pitch{xl, yl}, sp);
-                    IDSP_HIP_TRY(hipEventRecord(ss->join, ss->stream));
-                    IDSP_HIP_TRY(hipStreamWaitEvent(s, ss->join, 0));
-                    if (rc == IDSP_OK) note_kernel_also(" + stream_frame_major_few (lanes % 4, second stream)");
-                    return rc;
-                }
-            }
-        }
-        if constexpr (FmStagedOf<P>::value && P::HAS_IN && P::IN_DIV == 1 && sizeof(typename P::In) == 4 && sizeof(typename P::Out) == 4 && P::COST <= 120) {
-            const size_t head = lanes / (size_t(256) * kFmBlock) * (size_t(256) * kFmBlock), tail = lanes - head;
-            // (round 5: only when the whole rounds are 1, 2, 4, 8 or 16 times 65536 lanes — FULL 256-lane blocks on the sweep kernel; three
-            // or five rounds would be narrow blocks themselves, and the call is one sweep over all its lanes instead)
-            const size_t head_rounds = head / (size_t(256) * kFmBlock);
-            // ... a restriction of the SWEEP kernel's geometry: a processor it does not take at `head` lanes (SWEEP_MAX_LPT 2 or 4: cascades, chains of
-            // three sections and more) keeps round 3's split for any number of whole rounds (3 x 65536 + 8192 lanes of a 3-section chain: 0.65 against
-            // 0.57 as one launch with a ragged last round, profiles/r03_exp_split_streams.jsonl)
-            bool head_on_sweep = false;
-            if constexpr (LdsEligibleOf<P>::value) head_on_sweep = head != 0 && sweep_takes<P>(head);
-            const bool rounds_ok = !head_on_sweep || ((head_rounds & (head_rounds - 1)) == 0 && head_rounds <= 16);
-            if (head && tail && tail <= kSplitTailMax && rounds_ok && lanes % 4 == 0 && frames >= 16 && LdsEligibleOf<P>::value && !diag_on() && rows_ok &&
-                xl * 4 < (size_t(1) << 28) && yl * 4 < (size_t(1) << 28)) {
-                if (SideStream *ss = side_stream(s)) {
-                    IDSP_HIP_TRY(hipEventRecord(ss->fork, s));
-                    IDSP_HIP_TRY(hipStreamWaitEvent(ss->stream, ss->fork, 0));
-                    int rc = launch_stream<P>(prm, st, x, y, head, frames, layout, s, Pitch{xl, yl}, sp);
-                    // which kernel the whole rounds went to: the name that launch recorded (the dense-sweep kernel of fm_sweep.h, or the LDS-DMA
-                    // panel walk for the processors / shapes the sweep does not take)
-                    const char *const head_name = noted_kernel();
-                    const bool head_swept = head_name && std::strncmp(head_name, "stream_frame_major_sweep", 24) == 0;
-                    if (rc == IDSP_OK) {
-                        split_remainder_flag() = true;
-                        rc = launch_stream<P>(shift_lanes(prm, head, sizeof(typename P::In)), st + head, x + head, y + head, tail, frames, layout, ss->stream,
-                                              Pitch{xl, yl}, sp);
-                        split_remainder_flag() = false;
-                    }
-                    // join even after a failed launch: the caller's stream must not run ahead of whatever the side stream holds
-                    IDSP_HIP_TRY(hipEventRecord(ss->join, ss->stream));
-                    IDSP_HIP_TRY(hipStreamWaitEvent(s, ss->join, 0));
-                    if (rc == IDSP_OK)
-                        note_kernel(head_swept ? "stream_frame_major_sweep + stream_frame_major_staged (remainder, second stream)"
-                                               : "stream_frame_major_lds + stream_frame_major_staged (remainder, second stream)",
-                                    typeid(P).name());
-                    return rc;
-                }
-            }
-        }
-        if constexpr (FmStagedOf<P>::value && P::HAS_IN && P::IN_DIV == 1 && sizeof(typename P::In) == 4 && sizeof(typename P::Out) == 4 && P::COST <= thr::kPairMaxCost) {
-            // Few lanes, long calls, cheap single sections: one wave computes, one wave moves (stream_frame_major_pair above).
-            // (IDSP_DIAG=1 IDSP_NO_FM_PAIR=1: the staged single-wave kernel; IDSP_FM_PAIR_MAX_LANES=n: another upper lane count)
-            static const bool no_pair = diag_env("IDSP_NO_FM_PAIR") != nullptr;
-            static const size_t pair_max = diag_size("IDSP_FM_PAIR_MAX_LANES", thr::kPairMaxLanes);
-            // rows on the 64-byte grid only: off it the staged kernel's plain accesses and XCD-contiguous order (round 4) win — 16384 lanes of a 16385-lane
-            // tensor 0.315 ms here against 0.186 there
-            const bool grid64 = reinterpret_cast<uintptr_t>(x) % 64 == 0 && reinterpret_cast<uintptr_t>(y) % 64 == 0 && (xl * 4) % 64 == 0 && (yl * 4) % 64 == 0;
-            if (!no_pair && !split_remainder_flag() && lanes <= pair_max && frames >= thr::kPairMinFrames && lanes % 4 == 0 && grid64 && xl * 4 < (size_t(1) << 28) && yl * 4 < (size_t(1) << 28)) {
-                constexpr size_t bytes = 2 * size_t(kFmPairTile) + size_t(P::LDS_WORDS) * 4;
-                if (int rc = ensure_dyn_lds<&stream_frame_major_pair<P>>(bytes)) return rc;
-                note_kernel("stream_frame_major_pair[compute + mover wave per 32 lanes]", typeid(P).name());
-                hipLaunchKernelGGL((stream_frame_major_pair<P>), dim3(unsigned((lanes + 31) / 32)), dim3(2 * kWave), bytes, s, prm, st, x, y, lanes, frames, xl, yl, sp);
-                return launch_status();
-            }
-        }
-        if constexpr (P::HAS_IN && P::IN_DIV == 1 && sizeof(typename P::In) == 4) {
-            // Round 5: ONE dense sweep for any lane count (fm_sweep.h).  Every lane count from kSweepMinLanes up on rows that sit on the
-            // 64-byte grid goes here — whole multiples of 65536, ragged counts, 2^20 lanes alike — instead of panel walks of a persistent
-            // grid or a ragged last block.  (Lane counts a little above a multiple of 65536 were split above: their whole rounds come back
-            // here as full 256-lane blocks, the remainder runs beside them — 65552 lanes: 0.77 of the HBM peak against 0.54 as one sweep of
-            // half-empty blocks.)  (IDSP_DIAG=1 IDSP_NO_SWEEP=1: the round-4
-            // dispatch below.)  Rows off the 64-byte grid (dword alignment is all the requests and stores need): the same sweep with the
-            // blocks dealt to the XCDs in contiguous eighths.
-            static const bool no_sweep = diag_env("IDSP_NO_SWEEP") != nullptr;
-            static const size_t sweep_min = diag_size("IDSP_SWEEP_MIN_LANES", sizeof(typename P::Out) == 4 ? kSweepMinLanesFps : kSweepMinLanes);
-            static const bool cost_forced_ = diag_env("IDSP_LDS_COST") != nullptr, no_lds_ = diag_env("IDSP_NO_LDS_PATH") != nullptr;
-            static const bool grid64_only = diag_env("IDSP_SWEEP_GRID64_ONLY") != nullptr;  // IDSP_DIAG=1: rows off the 64-byte grid stay on round 3's kernel
-            const bool on_grid64 = reinterpret_cast<uintptr_t>(x) % 64 == 0 && reinterpret_cast<uintptr_t>(y) % 64 == 0 && (xl * sizeof(typename P::In)) % 64 == 0 &&
-                                   (yl * sizeof(typename P::Out)) % 64 == 0;
-            if constexpr (LdsEligibleOf<P>::value) {
-                // rows off the grid: from the lane count up where round 3's XCD-contiguous kernel would walk panels on a persistent grid (131076 dense
-                // lanes 0.56 -> 0.61, 100004 0.58 -> 0.65); below it that kernel is a single round itself and stays (65000 dense lanes 0.745)
-                static const size_t off_grid_min = diag_size("IDSP_SWEEP_OFFGRID_MIN_LANES", kLdsGridCap * size_t(kFmBlock));  // IDSP_DIAG=1
-                // ... and, 4-byte outputs, up to kSweepOffGridSmallMax lanes, where the alternative is the staged single-wave kernel (several frames per segment here: 40000 lanes at
-                // pitch + 4 0.51 -> 0.72 of the peak, 32768 0.52 -> 0.61, 49152 0.59 -> 0.69; 57344: 0.69 either way)
-                const bool off_grid_ok = !grid64_only && rows_ok && (lanes > off_grid_min || (sizeof(typename P::Out) == 4 && lanes <= thr::kSweepOffGridSmallMax));
-                if (!no_sweep && !cost_forced_ && !no_lds_ && (on_grid64 || off_grid_ok) && lanes % 4 == 0 && lanes >= sweep_min && frames >= thr::kSweepMinFrames &&
-                    sweep_takes<P>(lanes))
-                    return launch_sweep<P>(prm, st, x, y, lanes, frames, xl, yl, sp, s);
-            }
-        }
-        if constexpr (FmStagedOf<P>::value) {
-            // Few lanes (the chip is not full and every FrameMajor kernel below runs at its per-lane latency): the staged
-            // single-wave kernel.  Measured against the register-window and the LDS-DMA kernel (tools/tune_fm_small.hip,
-            // profiles/r02_tune_fm_small.jsonl; i32 DF1 x 4096 frames): 16384 lanes 0.147 ms (32 lanes per wave) against
-            // 0.211 / 0.335; 32768 lanes 0.211 (64) against 0.243 / 0.332; 8192 x 8192 0.247 against 0.384; 49152 lanes 0.32
-            // against 0.33 / 0.33; 65536 lanes 0.43 against 0.41 / 0.335.  Processors with COST > 120 gain only around
-            // 16384-32768 lanes (8-section cascade 0.44 against 0.48) and lose elsewhere.
-            // (IDSP_DIAG=1 IDSP_NO_FM_STAGED=1: never; IDSP_FM_LANES_PER_WAVE = 64 / 32 / 16 forces the form at any lane count)
-            static const bool no_fm_staged = diag_env("IDSP_NO_FM_STAGED") != nullptr;
-            static const size_t forced_flw = diag_size("IDSP_FM_LANES_PER_WAVE", 0);
-            constexpr size_t sz = sizeof(typename P::In);
-            constexpr bool heavy = P::COST > 120;
-            const bool in_range = heavy ? (lanes >= thr::kStagedHeavyMinLanes && lanes < thr::kStagedHeavyMaxLanes) : lanes < thr::kStagedMaxLanes;
-            if (!no_fm_staged && (forced_flw || in_range) && frames >= 16 && (lanes * sz) % 16 == 0 && rows_ok &&
-                xl * sz < (size_t(1) << 28) && yl * sz < (size_t(1) << 28)) {  // 32-bit offsets: up to 15 row pitches + 1 KiB inside a tile (16 lanes/wave)
-                // rows off the 64-byte grid: a 32-lane wave's 128-byte row pieces each straddle two lines; whole 256-byte pieces from 12288
-                // lanes (16384 lanes at pitch 16385: 0.19 ms with 64 lanes per wave, 0.27 with 32, 0.23 on the register-window kernel;
-                // 8192 lanes 0.175 / 0.147 / 0.21 — tools/exp_fm_unaligned_small.py, profiles/r03_exp_fm_unaligned_small.jsonl)
-                const bool off64 = (xl * sz) % 64 != 0 || (yl * sz) % 64 != 0 || reinterpret_cast<uintptr_t>(x) % 64 != 0 || reinterpret_cast<uintptr_t>(y) % 64 != 0;
-                // (round 4, with plain accesses on such rows the 32-lane form wins again up to ~25000 lanes: 16385 lanes 0.217 -> 0.182 ms,
-                // 12292 0.202 -> 0.163, 20484 0.240 -> 0.200, 24580 0.249 -> 0.223; 26628 0.255 with 64 against 0.268 with 32)
-                const size_t lw = forced_flw ? forced_flw : heavy ? 32 : lanes >= (off64 ? thr::kStaged64LanesOffGrid : thr::kStaged64Lanes) ? 64 : lanes >= thr::kStaged32Lanes ? 32 : 16;
-                auto go = [&](auto lw_tag) {
-                    constexpr int LW = decltype(lw_tag)::value;
-                    constexpr size_t bytes = size_t(kFmStagedTile) + size_t(P::LDS_WORDS) * 4;
-                    if (int rc = ensure_dyn_lds<&stream_frame_major_staged<P, LW>>(bytes)) return rc;
-                    note_kernel(LW == 64 ? "stream_frame_major_staged[64 lanes/wave]" : LW == 32 ? "stream_frame_major_staged[32 lanes/wave]" : "stream_frame_major_staged[16 lanes/wave]",
-                                typeid(P).name());
-                    // rows off the 64-byte grid: XCD-contiguous lane blocks (IDSP_DIAG=1 IDSP_STAGED_NO_XCDC=1: the plain order)
-                    static const bool no_xcdc = diag_env("IDSP_STAGED_NO_XCDC") != nullptr;
-                    const unsigned grid = unsigned((lanes + LW - 1) / LW);
-                    // ... and plain instead of nontemporal accesses there (bit 1; IDSP_DIAG=1 IDSP_STAGED_NT=1: nontemporal everywhere)
-                    static const bool all_nt = diag_env("IDSP_STAGED_NT") != nullptr;
-                    const int xcdc = (!no_xcdc && grid >= 64 && off64 ? 1 : 0) | (!all_nt && off64 ? 2 : 0);
-                    hipLaunchKernelGGL((stream_frame_major_staged<P, LW>), dim3(grid), dim3(kWave), bytes, s, prm, st, x, y, lanes, frames, xl, yl, sp, xcdc);
-                    return launch_status();
-                };
-                if constexpr (!heavy) {
-                    if (lw == 16) return go(std::integral_constant<int, 16>{});
-                    if (lw == 64) return go(std::integral_constant<int, 64>{});
-                }
-                return go(std::integral_constant<int, 32>{});
-            }
-        }
-        if constexpr (P::HAS_IN && P::IN_DIV == 1 && sizeof(typename P::In) == 4) {
-            // cheap per-sample arithmetic (the extra LDS hop and the two barriers per tile cost issue
-            // slots), whole 256-lane blocks, 16-byte aligned rows: LDS-DMA path
-            // Which processors take the LDS-DMA path: P::LDS_ELIGIBLE where the processor says so (measured per section type
-            // and section count against the register-window kernel, tools/tune_lds.hip, profiles/r02_tune_lds_heavy*.jsonl),
-            // else the cost estimate; IDSP_DIAG=1 IDSP_LDS_COST=n replaces both by `COST <= n`.
-            static const bool cost_forced = diag_env("IDSP_LDS_COST") != nullptr;
-            static const int lds_cost_max = int(diag_size("IDSP_LDS_COST", 120));
-            const bool eligible = cost_forced ? P::COST <= lds_cost_max : LdsEligibleOf<P>::value;
-            static const size_t lds_max_waves = diag_size("IDSP_LDS_MAX_WAVES", size_t(1) << 40);
-            static const bool no_lds = diag_env("IDSP_NO_LDS_PATH") != nullptr;
-            constexpr size_t ow = sizeof(typename P::Out) / 4;
-            // whole 256-lane blocks — or, for one-word outputs, any multiple of 4 lanes: the kernel's last block may be ragged
-            // (reference: any N in `Lanes<C>`, dsp-process/src/compose.rs:468)
-            if (!no_lds && eligible && waves >= lds_min_waves() && waves <= lds_max_waves && (lanes % kFmBlock == 0 || (ow == 1 && lanes % 4 == 0)) && rows_ok) {
-                // Grid (profiles/r02_exp_c5_*.jsonl).  Up to 384 workgroups: one per 256-lane block.  Beyond: a persistent
-                // grid of <= 256 workgroups (one per CU) that walks the lane blocks in column panels of equal rounds —
-                // 2^20 lanes: 0.68 of peak (0.61-0.75 by output placement) against 0.66 with 4096 workgroups and 0.615
-                // on the register-window kernel; 131072 lanes: 0.72 against 0.65 with 512 workgroups.  Two or four
-                // lanes per thread (whole-row sweeps by 256 workgroups) are available to processors that declare
-                // P::LDS_LPT_MAX; none does (see the kernel).  IDSP_DIAG=1 IDSP_LDS_LPT / IDSP_LDS_GRID override both.
-                static const size_t forced_lpt = diag_size("IDSP_LDS_LPT", 0);
-                static const size_t forced_grid = diag_size("IDSP_LDS_GRID", ~size_t(0));
-                const size_t nblocks = (lanes + kFmBlock - 1) / kFmBlock;
-                constexpr int kMaxLpt = LdsLptMaxOf<P>::value;
-                int lpt = 1;
-                if (lanes % kFmBlock != 0) {
-                    // ragged last block: one lane per thread only
-                } else if (forced_lpt) {
-                    lpt = int(forced_lpt) > kMaxLpt ? kMaxLpt : int(forced_lpt);
-                    while (lpt > 1 && nblocks % size_t(lpt) != 0) lpt >>= 1;
-                } else {
-                    for (int c = kMaxLpt; c > 1; c >>= 1)
-                        if (nblocks % size_t(c) == 0 && nblocks / size_t(c) >= 224 && nblocks / size_t(c) <= 320) {
-                            lpt = c;
-                            break;
-                        }
-                }
-                const size_t wgs = nblocks / size_t(lpt);
-                size_t grid = wgs;
-                if (forced_grid != ~size_t(0)) {
-                    if (forced_grid && wgs > forced_grid) grid = forced_grid;
-                } else if (wgs > kLdsGridCap) {
-                    const size_t rounds = (wgs + 255) / 256;
-                    grid = (wgs + rounds - 1) / rounds;
-                }
-                int rc = IDSP_OK;
-                // Ring depth: the processor's tuned depth for single-pass launches; persistent launches (large lane
-                // counts, row pitch >= 1.5 MiB) keep 7 tiles and the indexed form for every processor — depths 3-5 lose
-                // 15-20 % there (profiles/r02_exp_c5_matrix7.jsonl: 0.56 vs 0.68 at 2^20 lanes).
-                const bool persistent = grid < wgs;
-                auto go = [&](auto lpt_tag, auto deep) {
-                    constexpr int L = decltype(lpt_tag)::value;
-                    constexpr bool DEEP = decltype(deep)::value;
-                    constexpr int NB = DEEP ? 7 : LdsRingOf<P>::value;
-                    constexpr bool RUN = DEEP ? false : LdsRunOf<P>::value;
-                    constexpr size_t ts = L > kLdsT ? L : kLdsT;
-                    constexpr size_t bytes = (size_t(NB) * ts * kFmBlock + 2 * ts * kFmBlock * ow + P::LDS_WORDS) * 4;
-                    if ((rc = ensure_dyn_lds<&stream_frame_major_lds<P, NB, L, RUN>>(bytes))) return;
-                    note_kernel(L == 1 ? "stream_frame_major_lds" : L == 2 ? "stream_frame_major_lds[2 lanes/thread]" : "stream_frame_major_lds[4 lanes/thread]",
-                                typeid(P).name());
-                    hipLaunchKernelGGL((stream_frame_major_lds<P, NB, L, RUN>), dim3(unsigned(grid)), dim3(kFmBlock), bytes, s,
-                                       prm, st, x, y, lanes, frames, xl, yl, sp);
-                };
-                using Yes = std::true_type;
-                using No = std::false_type;
-                if constexpr (kMaxLpt >= 4) {
-                    if (lpt == 4) go(std::integral_constant<int, 4>{}, No{});
-                }
-                if constexpr (kMaxLpt >= 2) {
-                    if (lpt == 2) go(std::integral_constant<int, 2>{}, No{});
-                }
-                // rows that do not start on 64-byte boundaries (dense 65000-lane tensors, odd pitches): adjacent lane blocks on one XCD
-                // (IDSP_DIAG=1 IDSP_LDS_NO_XCDC=1: the plain block order, 0.58-0.64 of the peak on such rows instead of 0.67-0.71)
-                static const bool no_rot = diag_env("IDSP_LDS_NO_XCDC") != nullptr;
-                const bool misaligned = (xl * 4) % 64 != 0 || (yl * ow * 4) % 64 != 0 || reinterpret_cast<uintptr_t>(x) % 64 != 0 || reinterpret_cast<uintptr_t>(y) % 64 != 0;
-                {
-                    if (lpt == 1 && misaligned && !no_rot) {
-                        constexpr size_t bytes = (size_t(7) * kLdsT * kFmBlock + 2 * kLdsT * kFmBlock * ow + P::LDS_WORDS) * 4;
-                        if (int e = ensure_dyn_lds<&stream_frame_major_lds<P, 7, 1, false, true>>(bytes)) return e;
-                        note_kernel("stream_frame_major_lds[XCD-contiguous blocks]", typeid(P).name());
-                        hipLaunchKernelGGL((stream_frame_major_lds<P, 7, 1, false, true>), dim3(unsigned(grid)), dim3(kFmBlock), bytes, s, prm, st, x, y,
-                                           lanes, frames, xl, yl, sp);
-                        return launch_status();
-                    }
-                }
-                if (lpt == 1) {
-                    if (persistent && LdsRingOf<P>::value != 7)
-                        go(std::integral_constant<int, 1>{}, Yes{});
-                    else
-                        go(std::integral_constant<int, 1>{}, No{});
-                }
-                if (rc) return rc;
-                return launch_status();
-            }
-        }
-        // A CU's L1 moves ~10 B/cycle, so a launch must reach all 256 CUs: below 1024 waves (= 256
-        // workgroups of 4) use one wave per workgroup (16384 lanes in 256-thread blocks would run on 64 CUs).
-        const unsigned block = waves < 1024 ? unsigned(kWave) : unsigned(kFmBlock);
-        const unsigned grid = unsigned((lanes + block - 1) / block);
-        constexpr int kDeep = MaxU<P>::value, kShallow = kDeep < 8 ? kDeep : 8;
-        // XCD-contiguous lane blocks for rows off the 64-byte grid: what helps the LDS-DMA kernel HURTS this one — 65537 dense lanes
-        // 0.81 ms against 0.69 with the plain order (profiles/r03_perf_ragged_xcdc.jsonl) — so it is a diagnostic switch only
-        // (IDSP_DIAG=1 IDSP_FM_XCDC=1)
-        static const bool want_xcdc = diag_env("IDSP_FM_XCDC") != nullptr;
-        const int xcdc = want_xcdc && grid >= 64;
-        note_kernel(xcdc ? "stream_frame_major[XCD-contiguous blocks]" : "stream_frame_major", typeid(P).name());
-        if (waves <= 2048)
-            hipLaunchKernelGGL((stream_frame_major<P, kDeep>), dim3(grid), dim3(block), 0, s, prm, st, x, y, lanes, frames, xl, yl, xcdc, sp);
-        else
-            hipLaunchKernelGGL((stream_frame_major<P, kShallow>), dim3(grid), dim3(block), 0, s, prm, st, x, y, lanes, frames, xl, yl, xcdc, sp);
-    }
-    return launch_status();
+    StreamCall c;
+    c.lanes = lanes, c.frames = frames, c.layout = layout;
+    c.x = reinterpret_cast<uintptr_t>(x), c.y = reinterpret_cast<uintptr_t>(y);
+    c.pitch_x = pitch.x, c.pitch_y = pitch.y, c.state_pitch = state_pitch;
+    return launch_call<P>(prm, static_cast<uint32_t *>(state), x, y, c, s);
 }
 
 // Two-wave launch of a chain split into PA (first sections) and PB (the rest): FRAME_MAJOR only, 4-byte samples
@@ -1981,15 +1860,7 @@ int launch_duo(const typename PA::Params &pa, const typename PB::Params &pb, uin
     return launch_status();
 }
 
-// When a chain of m sections (per launch) goes to the two-wave kernel (IDSP_DIAG=1 IDSP_NO_DUO=1: never).  Measured at 4096 frames
-// (tools/exp_duo.hip, profiles/r03_exp_duo.jsonl): i32 chain of 4 at 65536 lanes 0.483 -> 0.426 ms, at 131072 lanes 0.829 -> 0.909;
-// i32 cascade of 8 at 32768 / 65536 / 131072 lanes 0.583 / 0.661 / 1.250 -> 0.482 / 0.578 / 1.066; and five to eight sections of a
-// plain chain are ONE pass over HBM instead of two.
-inline bool duo_wanted(size_t m, size_t lanes, int layout)
-{
-    static const bool off = diag_env("IDSP_NO_DUO") != nullptr;
-    if (off || layout != IDSP_FRAME_MAJOR || lanes < thr::kDuoMinLanes) return false;
-    return m >= 5 || (m == 4 && lanes <= thr::kDuo4MaxLanes);
-}
+// When a chain of m sections goes to it (stream_plan.h; IDSP_DIAG=1 IDSP_NO_DUO=1: never)
+inline bool duo_wanted(size_t m, size_t lanes, int layout) { return duo_wanted(m, lanes, layout, stream_switches()); }
 
 }  // namespace idsp

@@ -6,7 +6,7 @@ Three things live here and are shared by tests/test_stream_proc_cases.py (no GPU
 tests/test_gpu_stream_argument.py:
 
   * TRAITS: one row per form, copied by hand from phase_procs.h, rpll_procs.h and sweep_procs.h;
-  * expected_kernel(): the conditions of `launch_stream` and of `sweep_takes` / `launch_sweep` (fm_sweep.h) restated in Python for dense
+  * expected_kernel(): the conditions of `plan_stream` (stream_plan.h: the choice `launch_stream` makes, `sweep_takes` included) restated in Python for dense
     tensors without IDSP_DIAG, written from the launcher's source.  Every threshold is read from dispatch_thresholds.h by name when the
     module is imported; the few literals of the launcher itself are the named constants below, each with its source line;
   * CASES / UNREACHABLE: the case table and the branches no default dispatch of a form can reach;
@@ -51,14 +51,14 @@ def _constants(path):
 THR = _constants(os.path.join(CSRC, "dispatch_thresholds.h"))
 _LS = _constants(os.path.join(CSRC, "lane_stream.h"))
 K_WAVE, K_FM_BLOCK, K_LM_RUN = _LS["kWave"], _LS["kFmBlock"], _LS["kLmRun"]
-# literals of launch_stream itself (lane_stream.h), not thresholds of the header:
-FEW_MAX_LANES, FEW_MIN_FRAMES = 3, 64      # `lanes <= 3 && frames >= 64`: the whole call on stream_frame_major_few
-ODD_MIN_BODY, ODD_MIN_FRAMES = 8192, 16    # `odd && body >= 8192 && frames >= 16`: the lanes % 4 split
+# the small constants of the dispatch (stream_plan.h reads them from the header by these names; compared here as plain values):
+FEW_MAX_LANES, FEW_MIN_FRAMES = THR["kFewMaxLanes"], THR["kFewMinFrames"]        # `lanes <= 3 && frames >= 64`: the whole call on stream_frame_major_few
+ODD_MIN_BODY, ODD_MIN_FRAMES = THR["kOddSplitMinBody"], THR["kOddSplitMinFrames"]  # `odd && body >= 8192 && frames >= 16`: the lanes % 4 split
 ROUND_LANES = 256 * K_FM_BLOCK             # a whole round of the LDS-DMA kernel: 256 blocks of 256 lanes
-ROUND_MIN_FRAMES, ROUND_MAX_ROUNDS = 16, 16
-STAGED_MIN_FRAMES = 16                     # FrameMajor staged kernel: `frames >= 16`
-HEAVY_COST, LDS_COST = 120, 120            # `COST > 120` is heavy; LDS_ELIGIBLE defaults to `COST <= 120`
-SWEEP_MAX_GRID = 256                       # fm_sweep.h: one workgroup per CU
+ROUND_MIN_FRAMES, ROUND_MAX_ROUNDS = THR["kRoundsSplitMinFrames"], THR["kRoundsSplitMaxRounds"]
+STAGED_MIN_FRAMES = THR["kStagedMinFrames"]  # FrameMajor staged kernel: `frames >= 16`
+HEAVY_COST, LDS_COST = THR["kHeavyCost"], 120  # `COST > 120` is heavy; LDS_ELIGIBLE defaults to `COST <= 120` (lane_stream.h LdsEligibleOf)
+SWEEP_MAX_GRID = 256                       # stream_plan.h: one workgroup per CU
 
 # thresholds of the header that no condition of these forms' dispatch reads, with the reason
 NOT_CONSULTED = {
@@ -68,6 +68,15 @@ NOT_CONSULTED = {
     "kDuoMinLanes": "two-wave chain kernel: biquad chains only", "kDuo4MaxLanes": "two-wave chain kernel: biquad chains only",
     "kStaggerMinWorkgroups": "lockin_waves.h / dds.hip", "kStaggerMinFrames": "lockin_waves.h / dds.hip",
     "kStaggerMaxFrames": "lockin_waves.h / dds.hip", "kLockinStaggerTicks": "lockin_waves.h", "kFmDiscStaggerTicks": "dds.hip",
+    # compared as the plain constants above, not through _cmp: tests/test_stream_proc_cases.py `minimum()` holds a case on each side of them
+    "kHeavyCost": "HEAVY_COST: a compile-time condition on COST", "kFewMaxLanes": "FEW_MAX_LANES", "kFewMinFrames": "FEW_MIN_FRAMES",
+    "kOddSplitMinBody": "ODD_MIN_BODY", "kOddSplitMinFrames": "ODD_MIN_FRAMES", "kRoundsSplitMinFrames": "ROUND_MIN_FRAMES",
+    "kRoundsSplitMaxRounds": "ROUND_MAX_ROUNDS", "kStagedMinFrames": "STAGED_MIN_FRAMES", "kLmStagedMinRowBytes": "K_LM_RUN // 4 (lane_stream.h asserts the two equal)",
+    # launch parameters that do not change the kernel's name (grid order, block size, prefetch depth), or that no shipped processor reaches
+    "kStagedXcdcMinGrid": "the staged kernel's block order: not in the name", "kSweepXcdcMinGrid": "fewer than 8 workgroups of a sweep: below kSweepMinLanesFps",
+    "kSweepFpsMaxBlockLanes": "read directly by _launch_sweep (`g.bw <= 128`)", "kLdsLptMinGrid": "no processor declares LDS_LPT_MAX",
+    "kLdsLptMaxGrid": "no processor declares LDS_LPT_MAX", "kWindowBlockMinWaves": "the register-window kernel's block size: not in the name",
+    "kWindowDeepMaxWaves": "the register-window kernel's prefetch depth: not in the name", "kWindowXcdcMinGrid": "IDSP_FM_XCDC only",
 }
 
 _TRACE = None  # while set: (threshold, outcome, |value - threshold|) of every comparison expected_kernel evaluates
@@ -124,7 +133,7 @@ Geom = collections.namedtuple("Geom", "lpt grid bw rounds")
 
 
 def sweep_geometry(lanes, max_lpt, max_grid=SWEEP_MAX_GRID):
-    """fm_sweep.h `sweep_geometry`; None: not coverable"""
+    """stream_plan.h `sweep_geometry`; None: not coverable"""
     if lanes < 16 or max_lpt < 1:
         return None
     cap = max_grid * max_lpt * 256

@@ -1,0 +1,127 @@
+// stream_plan_cli — `plan_stream` (idsp_amd/csrc/stream_plan.h) from the command line, for tests/test_stream_plan.py: the dispatch of
+// `launch_stream` without a GPU.  Plain host C++, no HIP, no library.
+//
+// One case per line on stdin, one answer per line on stdout:
+//   plan <traits> <lanes> <frames> <FM|LM> <x mod 64> <y mod 64> <pitch x> <pitch y> [remainder] [no_side_stream] [IDSP_SWITCH=value ...]
+//        -> what idsp_last_kernel() reports for that call: `name<traits>suffixes`, a tab, the plan's launch parameters (pitches in elements,
+//           0 = dense; a switch counts as set under IDSP_DIAG=1, which therefore has to be among them — exactly as in the library)
+//   geom <lanes> <max_lpt>                     -> `grid x lpt x bw, rounds` of sweep_geometry, or `none`
+//   duo <sections> <lanes> <FM|LM> [IDSP_SWITCH=value ...]  -> 0 / 1 of duo_wanted
+#include <cstdio>
+#include <cstring>
+#include <iostream>
+#include <map>
+#include <sstream>
+#include <string>
+
+#include "../../idsp_amd/csrc/stream_plan.h"
+
+using namespace idsp;
+
+// The processors, by hand.  Values the processor does not declare are the detectors' defaults (lane_stream.h: LdsEligibleOf `COST <= 120`,
+// LdsLptMaxOf 1, LdsRingOf 8, FmStagedOf / LmStagedOf from the sample sizes, IN_DIV and BATCH; fm_sweep.h: SweepMaxLptOf `COST <= 120 ? 4 : 2`).
+static StreamTraits traits(bool has_in, int in_div, size_t in_bytes, size_t out_bytes, int cost, bool lds_eligible, int lds_ring, bool fm_staged, bool lm_staged,
+                           bool lm_one_form, int sweep_max_lpt)
+{
+    StreamTraits t;
+    t.has_in = has_in, t.in_div = in_div, t.in_bytes = in_bytes, t.out_bytes = out_bytes, t.cost = cost;
+    t.lds_eligible = lds_eligible, t.lds_lpt_max = 1, t.lds_ring = lds_ring;
+    t.fm_staged = fm_staged, t.lm_staged = lm_staged, t.lm_one_form = lm_one_form, t.sweep_max_lpt = sweep_max_lpt;
+    return t;
+}
+static const std::map<std::string, StreamTraits> kTraits = {
+    // biquad_sections.h `Chain<Df1I32<false>, N>` (COST = N * 50, LDS_RING 7 for one section else 4, LDS_ELIGIBLE = N <= LDS_MAX_N = 3,
+    // SWEEP_MAX_LPT 16 / 8 / 2 for N = 1 / 2 / 3): what idsp_biquad_i32_df1 runs for n = 1, 2, 3 sections
+    {"i32_df1", traits(true, 1, 4, 4, 50, true, 7, true, true, false, 16)},
+    {"i32_df1_x2", traits(true, 1, 4, 4, 100, true, 4, true, true, false, 8)},
+    {"i32_df1_x3", traits(true, 1, 4, 4, 150, true, 4, true, true, false, 2)},
+    // biquad_sections.h `Chain<Df2tF32<false>, 1>` (COST 22, LDS_RING 7, LDS_MAX_N 2): idsp_biquad_f32_df2t, one section
+    {"f32_df2t", traits(true, 1, 4, 4, 22, true, 7, true, true, false, 16)},
+    // phase_procs.h `ClampWrapProc` (COST 40, nothing else declared): a cheap 4-byte processor on the detectors' defaults
+    {"clamp_wrap", traits(true, 1, 4, 4, 40, true, 8, true, true, false, 4)},
+    // phase_procs.h `PllProc<0>` (COST 160, nothing else declared): a heavy 4-byte processor that is not LDS-eligible
+    {"pll", traits(true, 1, 4, 4, 160, false, 8, true, true, false, 2)},
+    // rpll_procs.h `RpllProc` (8-byte samples in and out, COST 150, nothing else declared)
+    {"rpll", traits(true, 1, 8, 8, 150, false, 8, true, true, false, 2)},
+    // phase_procs.h `UnwrapProc<1>` (int32 in, int64 out, COST 16, LDS_ELIGIBLE = false): an 8-byte output
+    {"unwrap_i64", traits(true, 1, 4, 8, 16, false, 8, false, false, false, 4)},
+    // lockin_stream_procs.h `LockinSplitProc<2, 2>` (IN_DIV 2, COST 70 + 40 * 4, BATCH 4): two threads share an input lane
+    {"lockin_split", traits(true, 2, 4, 4, 230, false, 8, false, false, false, 2)},
+};
+
+// name / also: what the launcher records; detail: the launch parameters of the plan that named the kernel
+static void print_plan(const StreamTraits &t, StreamCall c, const StreamSwitches &sw, std::string &name, std::string &also, std::string &detail)
+{
+    StreamPlan p = plan_stream(t, c, sw);
+    if (p.form == StreamForm::FmOddBeside) {
+        print_plan(t, lane_block(c, p, 0, p.body, false), sw, name, also, detail);  // the body records the name ...
+        also += stream_plan_also(p);                                                // ... and the few kernel is appended to it
+        return;
+    }
+    if (p.form == StreamForm::FmRoundsBeside) p.head_swept = plan_stream(t, lane_block(c, p, 0, p.head, false), sw).form == StreamForm::FmSweep;
+    name = stream_plan_name(p);
+    also = stream_plan_also(p) ? stream_plan_also(p) : "";
+    char text[256];
+    snprintf(text, sizeof text, "grid=%u lanes_per_wave=%d lanes_per_thread=%d deep_ring=%d xcdc=%d staged_flags=%d block=%u deep_window=%d head=%zu tail=%zu sweep=%ux%dx%u,%u,fps%u",
+             p.grid, p.lanes_per_wave, p.lanes_per_thread, int(p.deep_ring), int(p.xcdc), p.staged_flags, p.block, int(p.deep_window), p.head, p.tail, p.geom.grid,
+             p.geom.lpt, p.geom.bw, p.geom.rounds, p.geom.fps);
+    detail = text;
+}
+
+int main()
+{
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        std::istringstream in(line);
+        std::string cmd, word;
+        if (!(in >> cmd)) continue;
+        std::map<std::string, std::string> env;
+        auto getenv_ = [&](const char *name) -> const char * {
+            const auto diag = env.find("IDSP_DIAG");
+            if (diag == env.end() || atoi(diag->second.c_str()) == 0) return nullptr;  // common.h `diag_env`
+            const auto it = env.find(name);
+            return it == env.end() ? nullptr : it->second.c_str();
+        };
+        if (cmd == "geom") {
+            size_t lanes = 0;
+            int max_lpt = 0;
+            in >> lanes >> max_lpt;
+            SweepGeom g;
+            if (sweep_geometry(lanes, max_lpt, g))
+                printf("%u x %d x %u, %u\n", g.grid, g.lpt, g.bw, g.rounds);
+            else
+                printf("none\n");
+        } else if (cmd == "duo") {
+            size_t m = 0, lanes = 0;
+            std::string layout;
+            in >> m >> lanes >> layout;
+            while (in >> word) env[word.substr(0, word.find('='))] = word.find('=') == std::string::npos ? "" : word.substr(word.find('=') + 1);
+            printf("%d\n", int(duo_wanted(m, lanes, layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR, read_stream_switches(getenv_))));
+        } else if (cmd == "plan") {
+            std::string tn, layout;
+            StreamCall c;
+            size_t xo = 0, yo = 0;
+            in >> tn >> c.lanes >> c.frames >> layout >> xo >> yo >> c.pitch_x >> c.pitch_y;
+            if (!in || !kTraits.count(tn) || (layout != "FM" && layout != "LM")) {
+                printf("error: %s\n", line.c_str());
+                continue;
+            }
+            c.layout = layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR;
+            c.x = (uintptr_t(1) << 32) + xo, c.y = (uintptr_t(1) << 33) + yo;
+            while (in >> word) {
+                if (word == "remainder")
+                    c.remainder_of_split = true;
+                else if (word == "no_side_stream")
+                    c.no_side_stream = true;
+                else
+                    env[word.substr(0, word.find('='))] = word.find('=') == std::string::npos ? "" : word.substr(word.find('=') + 1);
+            }
+            std::string name, also, detail;
+            print_plan(kTraits.at(tn), c, read_stream_switches(getenv_), name, also, detail);
+            printf("%s<%s>%s\t%s\n", name.c_str(), tn.c_str(), also.c_str(), detail.c_str());
+        } else {
+            printf("error: %s\n", line.c_str());
+        }
+    }
+    return 0;
+}

@@ -11,6 +11,7 @@ import torch
 
 from idsp_amd import _abi
 from tests import _harness as H
+from tests._dispatch_cases import I32_FM, ODD, SWEEP  # the shape table, shared with tests/test_stream_plan.py (no GPU)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -43,30 +44,6 @@ def biquad_kernel(gpu, op, lanes, frames, layout, dtype, words, pitch=None, n=1)
     assert rc == 0, gpu.err()
     assert int(y.view(rows, pitch)[:, : (lanes if layout == FM else frames)].abs().max()) == 0, "zero input, zero state: zero output must have been written"
     return last(gpu)
-
-
-SWEEP = "stream_frame_major_sweep["
-ODD = " + stream_frame_major_few (lanes % 4, second stream)"
-# (lanes, expected start of the kernel name, expected end or None): i32 DF1, FrameMajor, dense rows
-I32_FM = [
-    (65536, SWEEP + "1 block/workgroup]<", None),                       # C2
-    (131072, SWEEP + "2 blocks/workgroup]<", None),                     # C5 shard at 8 GPUs
-    (262144, SWEEP + "4 blocks/workgroup]<", None),
-    (524288, SWEEP + "8 blocks/workgroup]<", None),
-    (1048576, SWEEP + "16 blocks/workgroup]<", None),                   # C5
-    (100000, SWEEP + "2 blocks/workgroup]<", None),                     # narrow blocks (208 lanes)
-    (65552, "stream_frame_major_sweep + stream_frame_major_staged (remainder, second stream)<", None),  # a little above one round
-    (65537, "stream_frame_major_lds[XCD-contiguous blocks]<", ODD),     # cliff: rows off the grid, last lane beside
-    (131073, SWEEP + "2 blocks/workgroup, XCD-contiguous]<", ODD),      # cliff: off the grid beyond 98304 lanes
-    (49152, SWEEP + "1 block/workgroup]<", None),
-    (32768, SWEEP + "1 block/workgroup]<", None),                       # several frames per segment
-    (32769, SWEEP + "1 block/workgroup, XCD-contiguous]<", ODD),        # cliff: rows off the grid, several frames per segment up to 53248 lanes
-    (24576, SWEEP + "1 block/workgroup]<", None),
-    (24560, "stream_frame_major_staged[32 lanes/wave]<", None),         # below kSweepMinLanesFps
-    (16384, "stream_frame_major_staged[32 lanes/wave]<", None),
-    (8192, "stream_frame_major_staged[32 lanes/wave]<", None),
-    (8176, "stream_frame_major_staged[16 lanes/wave]<", None),
-]
 
 
 @pytest.mark.parametrize("lanes,start,end", I32_FM, ids=[str(s[0]) for s in I32_FM])
