@@ -55,6 +55,33 @@ template <class S, int N>
 struct ChainParams {
     S sec[N];
 };
+// `fill` is one of the Fill* functors below
+template <class Fill, class S, int N>
+inline void fill_sections(const Fill &fill, S (&sec)[N])
+{
+    for (int k = 0; k < N; k++) fill(sec[k], size_t(k));
+}
+
+// The state of NS serial sections of W words each on one lock-in arm (lockin_generic.hip, lockin_waves_biquad.hip): words
+// `word0 + k W + w` of the lane's record, section-major
+template <int NS, int W = 4>
+struct SectionState {
+    uint32_t s[NS][W];
+    __device__ __forceinline__ void load(const uint32_t *st, size_t lanes, size_t lane, int word0)
+    {
+#pragma unroll
+        for (int k = 0; k < NS; k++)
+#pragma unroll
+            for (int w = 0; w < W; w++) s[k][w] = st[size_t(word0 + k * W + w) * lanes + lane];
+    }
+    __device__ __forceinline__ void store(uint32_t *st, size_t lanes, size_t lane, int word0) const
+    {
+#pragma unroll
+        for (int k = 0; k < NS; k++)
+#pragma unroll
+            for (int w = 0; w < W; w++) st[size_t(word0 + k * W + w) * lanes + lane] = s[k][w];
+    }
+};
 
 // ------------------------------------------------------------ i32 sections
 // src/iir/biquad.rs:366-383 (C = Q<i32,i64,F>): acc = b0*x0 + b1*x1 + b2*x2 +

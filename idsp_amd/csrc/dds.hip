@@ -11,13 +11,9 @@
 
 namespace idsp {
 
-// lockin_waves_{iq,arg,norm_sqr}.hip: one lane's work spread over 4 or 6 waves (lockin_waves.h)
-int lockin_waves_iq(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, void *y, size_t lanes, size_t frames, int layout,
-                    int waves, hipStream_t s, size_t pitch = 0);
-int lockin_waves_arg(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, void *y, size_t lanes, size_t frames, int layout,
-                     int waves, hipStream_t s, size_t pitch = 0);
-int lockin_waves_norm_sqr(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, void *y, size_t lanes, size_t frames,
-                          int layout, int waves, hipStream_t s, size_t pitch = 0);
+// lockin_waves_{iq,arg,norm_sqr}.hip: one lane's work spread over several waves, in the plan's form (lockin_waves.h; `plan.body` frames)
+using LockinWavesFn = int(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, void *y, size_t lanes, const LockinPlan &plan, hipStream_t s, size_t pitch);
+LockinWavesFn lockin_waves_iq, lockin_waves_arg, lockin_waves_norm_sqr;
 
 // lockin_stream_{iq,arg,norm_sqr}.hip, lowpass.hip: the stream processors behind the multi-wave kernels (lockin_stream_procs.h)
 int lockin_stream_iq(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout, bool split, hipStream_t s,
@@ -29,40 +25,39 @@ int lowpass_stream(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, in
 
 namespace {
 
-// The multi-wave kernels take FrameMajor always and LaneMajor for whole 16-frame batches on 16-byte aligned rows
-// (IDSP_LOCKIN_NO_WAVES=1 keeps everything on the one- / two-thread-per-lane stream kernels below).
-// Returns the wave count per 64 lanes, 0 = use the stream kernels.
-inline int lockin_waves_for(const void *x, const void *y, size_t lanes, size_t frames, int layout, bool heavy_readout, int arm_weight = 0)
+// What tells the three phase-form entries with lowpass arms apart: the waves launcher, the elements of y per frame and the stream
+// launcher (only `Complex<i32>` has a two-thread split)
+constexpr LockinWavesFn *kPhaseWaves[3] = {lockin_waves_iq, lockin_waves_arg, lockin_waves_norm_sqr};  // [MODE_*]
+template <int MODE, class Y>
+int lockin_phase_stream(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, Y *y, size_t lanes, size_t frames, int layout, bool split, hipStream_t s, size_t pitch)
 {
-    static const bool off = diag_env("IDSP_LOCKIN_NO_WAVES") != nullptr;
-    static const int forced = [] {
-        const char *e = diag_env("IDSP_LOCKIN_WAVES");
-        return e ? atoi(e) : 0;
-    }();
-    if (off || frames == 0) return 0;
-    if (lanes >= (size_t(1) << 28)) return 0;  // 32-bit thread offsets inside a row (8-byte elements, 3 input rows of 4 lanes bytes)
-    if (layout == IDSP_LANE_MAJOR && !(frames % 16 == 0 && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16 == 0))
-        return 0;
-    if (forced == 4 || forced == 6) return forced;
-    // FrameMajor up to one workgroup per CU: six waves (four read-out waves) with 16-frame batches — the read-out path is what an interval
-    // waits for there (`[Lowpass<1>; 1]` 0.183 -> 0.156 ms, `[Lowpass<2>; 1]`->arg 0.324 -> 0.283 at 16384 lanes x 4096, profiles/r03_perf_c4small.jsonl;
-    // `[Lowpass<N>; 2]` is the stage-wave kernel's at these lane counts).  Two 6-wave workgroups with 16-frame batches do not share a CU, so not above.
-    if (layout == IDSP_FRAME_MAJOR && lanes <= 16384) return 6;
-    // measured at 4096 frames (arg read-out): 6 waves 0.64 ms at 32768 lanes (4 waves: 0.73), 4 waves 1.07 ms at 65536 (6: 1.12)
-    // (`arm_weight` = order x cascade: with six and more second-order-equivalents per arm the arm waves are the longer path again and the four-wave
-    // form with 16-frame batches wins: `[Lowpass<2>; 4]` -> arg at 32768 lanes 0.58 against 0.74 ms, profiles/r03_perf_c4small_32768.jsonl)
-    return heavy_readout && lanes <= kSplitMaxLanes && arm_weight < 6 ? 6 : 4;
+    if constexpr (MODE == MODE_IQ)
+        return lockin_stream_iq(cfg, state, x, y, lanes, frames, layout, split, s, pitch);
+    else if constexpr (MODE == MODE_ARG)
+        return lockin_stream_arg(cfg, state, x, y, lanes, frames, layout, s, pitch);
+    else
+        return lockin_stream_norm_sqr(cfg, state, x, y, lanes, frames, layout, s, pitch);
 }
 
-// LaneMajor rows that are not whole 16-frame batches (round 4): the multi-wave kernel takes the whole batches of every row at the call's
-// row pitch and a stream kernel the last frames % 16 behind it (same stream; the state carries over as between two calls).  Rows
-// must keep their 16-byte alignment: frames % 4 == 0.  Returns the frames of the first part, 0 = the call is not of that kind.
-inline size_t lockin_lm_body(const void *x, const void *y, size_t frames, int layout)
+// idsp_lockin_i32_process / _arg / _norm_sqr: plan_lockin (lockin_plan.h) says which kernels, this runs them
+template <int MODE, class Y>
+int lockin_phase(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, Y *y, size_t lanes, size_t frames, int layout, void *stream)
 {
-    static const bool off = diag_env("IDSP_LOCKIN_NO_LM_TAIL") != nullptr;
-    if (off || layout != IDSP_LANE_MAJOR || frames % 16 == 0 || frames % 4 != 0 || frames < 32) return 0;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16 != 0) return 0;
-    return frames - frames % 16;
+    int rc = lockin_cfg_check(cfg);
+    if (rc) return rc;
+    if ((rc = check_stream_args(cfg, 1, state, x, y, lanes, frames, layout))) return rc;
+    if (lanes == 0) return IDSP_OK;
+    const hipStream_t s = as_stream(stream);
+    const LockinPlan plan = lockin_plan_for(LockinArms::Lowpass, LockinLo::Phase, MODE, cfg->order, cfg->cascade, x, y, lanes, frames, layout);
+    if (plan.form == LockinForm::Stream) return lockin_phase_stream<MODE>(cfg, state, x, y, lanes, frames, layout, plan.split, s, 0);
+    // WavesTail: the multi-wave kernel takes the whole batches of every LaneMajor row at the call's row pitch and a stream kernel the last
+    // frames % 16 behind it (same stream; the state carries over as between two calls)
+    const bool tail = plan.form == LockinForm::WavesTail;
+    rc = kPhaseWaves[MODE](cfg, state, x, y, lanes, plan, s, tail ? frames : 0);
+    if (rc || !tail) return rc;
+    rc = lockin_phase_stream<MODE>(cfg, state, x + plan.body, y + (MODE == MODE_IQ ? 2 : 1) * plan.body, lanes, frames - plan.body, layout, false, s, frames);
+    if (rc == IDSP_OK) note_kernel(lockin_plan_name(plan));
+    return rc;
 }
 
 // ------------------------------------------------------------- processors
@@ -569,7 +564,7 @@ int idsp_dds_i32(void *state, int32_t *out, size_t lanes, size_t frames, int lay
     if (lanes == 0) return IDSP_OK;
     static const bool no_circle = diag_env("IDSP_DDS_NO_CIRCLE") != nullptr;
     const bool circle = !no_circle && layout == IDSP_FRAME_MAJOR && frames >= 256;
-    if (lanes <= kSplitMaxLanes) {
+    if (lanes <= lockin_switches().split_max_lanes) {  // thr::kSplitMaxLanes
         DdsSplitProc::Params ps{0};
         if (circle) {
             DdsSplitProcT<true>::Params pc{0};
@@ -578,7 +573,7 @@ int idsp_dds_i32(void *state, int32_t *out, size_t lanes, size_t frames, int lay
         return launch_stream<DdsSplitProc>(ps, state, static_cast<const int32_t *>(nullptr), out, 2 * lanes, frames, layout,
                                            as_stream(stream));
     }
-    // one thread per lane (above kSplitMaxLanes) keeps the 512-byte table: 65536 lanes x 4096 run 0.36-0.37 ms with it and 0.46 with the
+    // one thread per lane (above thr::kSplitMaxLanes) keeps the 512-byte table: 65536 lanes x 4096 run 0.36-0.37 ms with it and 0.46 with the
     // full-circle table, 24- or 16-byte entries alike (profiles/r03_perf_dds_circle.jsonl, r03_perf_dds_one_circle.jsonl)
     DdsProc::Params p{0};
     return launch_stream<DdsProc>(p, state, static_cast<const int32_t *>(nullptr), reinterpret_cast<Cplx *>(out), lanes,
@@ -594,62 +589,19 @@ size_t idsp_lockin_state_words(const idsp_lockin_i32 *cfg)
 int idsp_lockin_i32_process(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, int32_t *y, size_t lanes,
                             size_t frames, int layout, void *stream)
 {
-    int rc = lockin_cfg_check(cfg);
-    if (rc) return rc;
-    if ((rc = check_stream_args(cfg, 1, state, x, y, lanes, frames, layout))) return rc;
-    if (lanes == 0) return IDSP_OK;
-    if (const int waves = lockin_waves_for(x, y, lanes, frames, layout, false))
-        return lockin_waves_iq(cfg, state, x, y, lanes, frames, layout, waves, as_stream(stream));
-    if (const size_t body = lockin_lm_body(x, y, frames, layout)) {
-        if (const int waves = lockin_waves_for(x, y, lanes, body, layout, false)) {
-            if ((rc = lockin_waves_iq(cfg, state, x, y, lanes, body, layout, waves, as_stream(stream), frames))) return rc;
-            rc = lockin_stream_iq(cfg, state, x + body, y + 2 * body, lanes, frames - body, layout, false, as_stream(stream), frames);
-            if (rc == IDSP_OK) note_kernel("lockin_waves_kernel + stream kernel (last frames % 16)");
-            return rc;
-        }
-    }
-    // too few lanes to give every SIMD a wave: put the I and Q arms on separate threads (both layouts)
-    return lockin_stream_iq(cfg, state, x, y, lanes, frames, layout, lanes <= kSplitMaxLanes, as_stream(stream));
+    return lockin_phase<MODE_IQ>(cfg, state, x, y, lanes, frames, layout, stream);
 }
 
 int idsp_lockin_i32_arg(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames,
                         int layout, void *stream)
 {
-    int rc = lockin_cfg_check(cfg);
-    if (rc) return rc;
-    if ((rc = check_stream_args(cfg, 1, state, x, y, lanes, frames, layout))) return rc;
-    if (lanes == 0) return IDSP_OK;
-    if (const int waves = lockin_waves_for(x, y, lanes, frames, layout, true, cfg->order * cfg->cascade))
-        return lockin_waves_arg(cfg, state, x, y, lanes, frames, layout, waves, as_stream(stream));
-    if (const size_t body = lockin_lm_body(x, y, frames, layout)) {
-        if (const int waves = lockin_waves_for(x, y, lanes, body, layout, true, cfg->order * cfg->cascade)) {
-            if ((rc = lockin_waves_arg(cfg, state, x, y, lanes, body, layout, waves, as_stream(stream), frames))) return rc;
-            rc = lockin_stream_arg(cfg, state, x + body, y + body, lanes, frames - body, layout, as_stream(stream), frames);
-            if (rc == IDSP_OK) note_kernel("lockin_waves_kernel + stream kernel (last frames % 16)");
-            return rc;
-        }
-    }
-    return lockin_stream_arg(cfg, state, x, y, lanes, frames, layout, as_stream(stream));
+    return lockin_phase<MODE_ARG>(cfg, state, x, y, lanes, frames, layout, stream);
 }
 
 int idsp_lockin_i32_norm_sqr(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, int64_t *y, size_t lanes,
                              size_t frames, int layout, void *stream)
 {
-    int rc = lockin_cfg_check(cfg);
-    if (rc) return rc;
-    if ((rc = check_stream_args(cfg, 1, state, x, y, lanes, frames, layout))) return rc;
-    if (lanes == 0) return IDSP_OK;
-    if (const int waves = lockin_waves_for(x, y, lanes, frames, layout, false))
-        return lockin_waves_norm_sqr(cfg, state, x, y, lanes, frames, layout, waves, as_stream(stream));
-    if (const size_t body = lockin_lm_body(x, y, frames, layout)) {
-        if (const int waves = lockin_waves_for(x, y, lanes, body, layout, false)) {
-            if ((rc = lockin_waves_norm_sqr(cfg, state, x, y, lanes, body, layout, waves, as_stream(stream), frames))) return rc;
-            rc = lockin_stream_norm_sqr(cfg, state, x + body, y + body, lanes, frames - body, layout, as_stream(stream), frames);
-            if (rc == IDSP_OK) note_kernel("lockin_waves_kernel + stream kernel (last frames % 16)");
-            return rc;
-        }
-    }
-    return lockin_stream_norm_sqr(cfg, state, x, y, lanes, frames, layout, as_stream(stream));
+    return lockin_phase<MODE_NORM_SQR>(cfg, state, x, y, lanes, frames, layout, stream);
 }
 
 int idsp_fm_disc_i32(const idsp_fm_disc *cfg, void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames,
@@ -661,9 +613,7 @@ int idsp_fm_disc_i32(const idsp_fm_disc *cfg, void *state, const int32_t *x, int
     if (lanes == 0 || frames == 0) return IDSP_OK;
     FmDiscProc::Params p;
     p.carrier = cfg->carrier;
-    for (int i = 0; i < 5; i++) p.sec.ba[i] = cfg->deemph.ba[i];
-    p.sec.frac = cfg->deemph.frac;
-    p.sec.u = 0, p.sec.mn = INT32_MIN, p.sec.mx = INT32_MAX;
+    bq::FillI32{&cfg->deemph}(p.sec, 0);
     // FRAME_MAJOR: the discriminator on four front waves, the deemphasis biquad on a fifth (IDSP_DIAG=1 IDSP_FM_DISC_WAVES=0: the
     // one-thread-per-lane stream kernel; = 3: three front waves)
     // Up to 81920 lanes: beyond, the stream kernel has two waves per SIMD itself and fewer instructions per sample (no LDS hand-over,

@@ -7,6 +7,7 @@
 #include "cossin_table.h"
 #include "biquad_sections.h"
 #include "lane_stream.h"
+#include "lockin_plan.h"
 
 namespace idsp {
 namespace {
@@ -19,16 +20,53 @@ __device__ const uint32_t d_cossin_table[1 << kCossinDepth] = {
 #undef T8
 };
 
-// Largest lane count that still runs the I and Q arms on two threads (IDSP_SPLIT_MAX_LANES overrides).
-inline size_t split_max_lanes()
+// The kernel-selection switches of the lock-in family, read once per process (honoured only with IDSP_DIAG=1: diag_env)
+inline const LockinSwitches &lockin_switches()
 {
-    static const size_t v = [] {
-        const char *e = diag_env("IDSP_SPLIT_MAX_LANES");
-        return e ? size_t(strtoull(e, nullptr, 10)) : size_t(40960);
-    }();
-    return v;
+    static const LockinSwitches sw = read_lockin_switches(diag_env);
+    return sw;
 }
-#define kSplitMaxLanes split_max_lanes()
+
+// plan_lockin (lockin_plan.h) for a call of one of the entries
+inline LockinPlan lockin_plan_for(LockinArms arms, LockinLo lo, int readout, int order, int cascade, const void *x, const void *y, size_t lanes, size_t frames,
+                                  int layout)
+{
+    LockinCall c;
+    c.arms = arms, c.lo = lo, c.readout = readout, c.order = order, c.cascade = cascade;
+    c.lanes = lanes, c.frames = frames, c.layout = layout;
+    c.x = reinterpret_cast<uintptr_t>(x), c.y = reinterpret_cast<uintptr_t>(y);
+    c.tuned_device = layout == IDSP_LANE_MAJOR && stagger_tuned_device();  // read for the LaneMajor input forms only
+    return plan_lockin(c, lockin_switches());
+}
+
+// f(N, K) / f(NS) with the configuration as compile-time constants: `[Lowpass<N>; K]`, 1..4 biquad sections (callers have checked n)
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class F>
+inline int for_nk(const idsp_lockin_i32 *cfg, F &&f)
+{
+    switch (cfg->cascade >= 1 && cfg->cascade <= IDSP_LOCKIN_MAX_CASCADE ? 10 * cfg->order + cfg->cascade : 0) {
+        case 11: return f(int_c<1>{}, int_c<1>{});
+        case 12: return f(int_c<1>{}, int_c<2>{});
+        case 13: return f(int_c<1>{}, int_c<3>{});
+        case 14: return f(int_c<1>{}, int_c<4>{});
+        case 21: return f(int_c<2>{}, int_c<1>{});
+        case 22: return f(int_c<2>{}, int_c<2>{});
+        case 23: return f(int_c<2>{}, int_c<3>{});
+        case 24: return f(int_c<2>{}, int_c<4>{});
+        default: return fail(IDSP_EINVAL, "unsupported lowpass configuration");
+    }
+}
+template <class F>
+inline int for_sections(size_t n, F &&f)
+{
+    switch (n) {
+        case 1: return f(int_c<1>{});
+        case 2: return f(int_c<2>{});
+        case 3: return f(int_c<3>{});
+        default: return f(int_c<4>{});
+    }
+}
 
 struct Cplx {
     int32_t re, im;

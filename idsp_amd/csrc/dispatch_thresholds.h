@@ -2,7 +2,8 @@
 // (round 5; VERDICT round 4, "upkeep").  Each was measured on MI355X boxes that differ by 3-5 %, so none of them is sharp; the file each
 // comes from is named, profiles/NOTES.md has the numbers, and tests/test_gpu_dispatch_table.py pins the kernel taken at every BASELINE
 // shape and on both sides of every cliff listed here; tests/test_stream_plan.py pins the same table and both sides of every threshold without
-// a GPU, through `plan_stream` (stream_plan.h), which is the one reader of what follows.
+// a GPU, through `plan_stream` (stream_plan.h), which is the one reader of what follows — but for the lock-in section, whose one reader is
+// `plan_lockin` (lockin_plan.h; tests/test_lockin_plan.py pins both sides of each of its names the same way).
 #pragma once
 
 #include <cstddef>
@@ -66,6 +67,21 @@ constexpr size_t kLmStagedMinRowBytes = 128;
 constexpr unsigned kStaggerMinWorkgroups = 512;                     // launches of at least two workgroups per CU
 constexpr size_t kStaggerMinFrames = 2048, kStaggerMaxFrames = 8192;  // long enough to pay, short enough not to drift apart anyway
 constexpr unsigned kLockinStaggerTicks = 600, kFmDiscStaggerTicks = 1200;  // 10 ns ticks between the four CU groups of an XCD
+
+// ---- lock-in (plan_lockin, lockin_plan.h; the measurements are quoted where each is read) ------------------------------------------
+// largest lane count that still runs the I and Q arms on two threads of the stream kernels (IDSP_SPLIT_MAX_LANES overrides); the multi-wave
+// kernel's 16-frame batches and the six-wave form of the `arg` read-out end at the same count
+constexpr size_t kSplitMaxLanes = 40960;
+// FrameMajor up to one workgroup per CU: six waves per 64 lanes with 16-frame batches; the stage-wave kernel with one lane group per workgroup
+constexpr size_t kLockinSixWavesMaxLanes = 16384, kLockinStagesOneGroupMaxLanes = 16384;
+// ... above, six waves for the `arg` read-out only while an arm is lighter than this many second-order equivalents (order x cascade)
+constexpr int kLockinSixWavesArmWeight = 6;
+// four workgroups per CU (above the first, up to the second): 16-frame batches again
+constexpr size_t kLockinB16MinLanes = 49152, kLockinB16MaxLanes = 65536;
+// the multi-wave kernels keep 32-bit thread offsets inside a row: fewer lanes than this (2^28)
+constexpr size_t kLockinWavesMaxLanes = 268435456;
+// LaneMajor rows that are not whole batches: body on the multi-wave kernel + tail on a stream kernel from this many frames
+constexpr size_t kLockinTailMinFrames = 32;
 
 }  // namespace thr
 }  // namespace idsp

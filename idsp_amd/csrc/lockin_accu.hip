@@ -11,18 +11,7 @@ template <template <int, int> class Proc, class OutT>
 int dispatch_accu_nk(const idsp_lockin_i32 *cfg, const LpAccuParams &p, void *state, const int32_t *x, OutT *y, size_t lanes, size_t frames, int layout,
                      hipStream_t s)
 {
-#define IDSP_CASE(N, K) \
-    if (cfg->order == N && cfg->cascade == K) return launch_stream<Proc<N, K>>(p, state, x, y, lanes, frames, layout, s)
-    IDSP_CASE(1, 1);
-    IDSP_CASE(1, 2);
-    IDSP_CASE(1, 3);
-    IDSP_CASE(1, 4);
-    IDSP_CASE(2, 1);
-    IDSP_CASE(2, 2);
-    IDSP_CASE(2, 3);
-    IDSP_CASE(2, 4);
-#undef IDSP_CASE
-    return fail(IDSP_EINVAL, "unsupported lowpass configuration");
+    return for_nk(cfg, [&](auto n, auto k) { return launch_stream<Proc<decltype(n)::value, decltype(k)::value>>(p, state, x, y, lanes, frames, layout, s); });
 }
 
 }  // namespace
@@ -34,8 +23,7 @@ extern "C" int idsp_lockin_i32_accu_process(const idsp_lockin_i32 *cfg, const id
                                             int32_t *y, size_t lanes, size_t updates, int layout, void *stream)
 {
     // the checks of idsp_lockin_i32_lo_process and of idsp_accu_lo_i32; an empty call (no lanes or no updates) touches no buffer and is IDSP_OK
-    if (!cfg || (cfg->order != 1 && cfg->order != 2) || cfg->cascade < 1 || cfg->cascade > IDSP_LOCKIN_MAX_CASCADE)
-        return fail(IDSP_EINVAL, "lock-in configuration: order 1..2, cascade 1..%d", IDSP_LOCKIN_MAX_CASCADE);
+    if (int rc = lockin_cfg_check(cfg)) return rc;
     if (!lo_cfg) return fail(IDSP_EINVAL, "lo_cfg is NULL");
     if (lo_cfg->batch_log2 < 0 || lo_cfg->batch_log2 > 24) return fail(IDSP_EINVAL, "batch_log2 = %d not in 0..24", lo_cfg->batch_log2);
     if (updates > ((size_t(1) << 40) >> lo_cfg->batch_log2)) return fail(IDSP_EINVAL, "updates << batch_log2 out of range");
@@ -55,6 +43,6 @@ extern "C" int idsp_lockin_i32_accu_process(const idsp_lockin_i32 *cfg, const id
     p.harmonic = uint32_t(lo_cfg->harmonic), p.offset = uint32_t(lo_cfg->offset);
     p.k = uint32_t(lo_cfg->batch_log2), p.jmask = (uint32_t(1) << lo_cfg->batch_log2) - 1u;
     // the I and Q arms on two threads up to the lane count where idsp_lockin_i32_process does so on its stream path
-    if (lanes <= kSplitMaxLanes) return dispatch_accu_nk<LockinAccuSplitProc, int32_t>(cfg, p, state, x, y, 2 * lanes, frames, layout, as_stream(stream));
+    if (lanes <= lockin_switches().split_max_lanes) return dispatch_accu_nk<LockinAccuSplitProc, int32_t>(cfg, p, state, x, y, 2 * lanes, frames, layout, as_stream(stream));
     return dispatch_accu_nk<LockinAccuProc, Cplx>(cfg, p, state, x, reinterpret_cast<Cplx *>(y), lanes, frames, layout, as_stream(stream));
 }

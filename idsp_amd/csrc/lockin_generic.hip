@@ -16,61 +16,29 @@
 
 namespace idsp {
 
-// lockin_waves_biquad.hip: the multi-wave lock-in kernel with the biquad chain as its arm functor
-int lockin_waves_biquad_iq(const idsp_biquad_i32 *sec, size_t n, void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames,
-                           int layout, hipStream_t s, size_t pitch = 0);
+// lockin_waves_biquad.hip, lockin_waves_lo.hip: the multi-wave lock-in kernel with these arms, in the plan's form (`plan.body` frames)
+int lockin_waves_biquad_iq(const idsp_biquad_i32 *sec, size_t n, void *state, const int32_t *x, int32_t *y, size_t lanes, const LockinPlan &plan, hipStream_t s,
+                           size_t pitch);
 int lockin_waves_biquad_lo(const idsp_biquad_i32 *sec, size_t n, void *state, const int32_t *x, const int32_t *lo, int32_t *y, size_t lanes,
-                           size_t frames, int layout, hipStream_t s, size_t pitch = 0);
-int lockin_waves_lowpass_lo(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, const int32_t *lo, int32_t *y, size_t lanes, size_t frames,
-                            int layout, hipStream_t s, size_t pitch = 0);  // lockin_waves_lo.hip
+                           const LockinPlan &plan, hipStream_t s, size_t pitch);
+int lockin_waves_lowpass_lo(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, const int32_t *lo, int32_t *y, size_t lanes, const LockinPlan &plan,
+                            hipStream_t s, size_t pitch);
 int lockin_waves_biquad_lo_f32(const idsp_biquad_f32 *sec, size_t n, void *state, const float *x, const float *lo, float *y, size_t lanes,
-                               size_t frames, int layout, hipStream_t s, size_t pitch = 0);
+                               const LockinPlan &plan, hipStream_t s, size_t pitch);
 
 namespace {
 
 typedef int32_t cplx_i32 __attribute__((ext_vector_type(2)));
 typedef float cplx_f32 __attribute__((ext_vector_type(2)));
 
-// Shapes the multi-wave kernel takes: FrameMajor always, LaneMajor for whole 16-frame batches on 16-byte aligned rows (as for
-// the lowpass arms, dds.hip lockin_waves_for).  IDSP_DIAG=1 IDSP_LOCKIN_NO_WAVES=1: the one-thread-per-lane kernels of this file.
-inline bool waves_take(const void *x, const void *y, size_t lanes, size_t frames, int layout)
-{
-    static const bool no_waves = diag_env("IDSP_LOCKIN_NO_WAVES") != nullptr;
-    const bool lm_ok = frames % 16 == 0 && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16 == 0;
-    return !no_waves && lanes < (size_t(1) << 28) && (layout == IDSP_FRAME_MAJOR || lm_ok);
-}
-
-// LaneMajor rows of 32 + 4 k frames that are not whole batches (round 4): the frames of the part the multi-wave kernel takes at the call's row pitch
-// (the last frames % 16 follow on a stream kernel, same stream), 0 = the call is not of that kind
-inline size_t lm_body(const void *x, const void *y, size_t lanes, size_t frames, int layout)
-{
-    if (layout != IDSP_LANE_MAJOR || frames < 32 || frames % 4 != 0 || frames % 16 == 0) return 0;
-    return waves_take(x, y, lanes, frames - frames % 16, layout) ? frames - frames % 16 : 0;
-}
-
 // n serial sections on one arm, state words at `word0` (section-major, {x0,x1,y0,y1} each)
 template <class Sec, int NS>
-struct Arm {
-    uint32_t s[NS][Sec::W];
-    __device__ __forceinline__ void load(const uint32_t *st, size_t lanes, size_t lane, int word0)
-    {
-#pragma unroll
-        for (int k = 0; k < NS; k++)
-#pragma unroll
-            for (int w = 0; w < Sec::W; w++) s[k][w] = st[size_t(word0 + k * Sec::W + w) * lanes + lane];
-    }
-    __device__ __forceinline__ void store(uint32_t *st, size_t lanes, size_t lane, int word0) const
-    {
-#pragma unroll
-        for (int k = 0; k < NS; k++)
-#pragma unroll
-            for (int w = 0; w < Sec::W; w++) st[size_t(word0 + k * Sec::W + w) * lanes + lane] = s[k][w];
-    }
+struct Arm : bq::SectionState<NS, Sec::W> {
     template <class P>
     __device__ __forceinline__ typename Sec::T step(const P &p, typename Sec::T x)
     {
 #pragma unroll
-        for (int k = 0; k < NS; k++) x = Sec::step(p.sec[k], s[k], x);
+        for (int k = 0; k < NS; k++) x = Sec::step(p.sec[k], this->s[k], x);
         return x;
     }
 };
@@ -218,24 +186,6 @@ struct LockinBiquadLoProc {
 
 bool sections_ok(const void *sections, size_t n) { return sections && n >= 1 && n <= IDSP_LOCKIN_MAX_SECTIONS; }
 
-template <int NS>
-void fill_i32(const idsp_biquad_i32 *sec, bq::SecI32 (&out)[NS])
-{
-    for (int k = 0; k < NS; k++) {
-        for (int i = 0; i < 5; i++) out[k].ba[i] = sec[k].ba[i];
-        out[k].frac = sec[k].frac;
-        out[k].u = 0, out[k].mn = INT32_MIN, out[k].mx = INT32_MAX;
-    }
-}
-template <int NS>
-void fill_f32(const idsp_biquad_f32 *sec, bq::SecF32 (&out)[NS])
-{
-    for (int k = 0; k < NS; k++) {
-        for (int i = 0; i < 5; i++) out[k].ba[i] = sec[k].ba[i];
-        out[k].u = 0.f, out[k].mn = -__builtin_inff(), out[k].mx = __builtin_inff();
-    }
-}
-
 int check_lo_args(const void *cfg, const void *state, const void *x, const void *lo, const void *y, size_t lanes, size_t frames, int layout)
 {
     int rc = check_stream_args(cfg, 1, state, x, y, lanes, frames, layout);
@@ -246,42 +196,59 @@ int check_lo_args(const void *cfg, const void *state, const void *x, const void 
     if (reinterpret_cast<uintptr_t>(lo) % 8 || reinterpret_cast<uintptr_t>(y) % 8)
         return fail(IDSP_EINVAL, "lo and y hold Complex pairs: both must be 8-byte aligned");
     // three separate buffers (include/idsp_hip.h): x is walked by a side pointer while lo streams through the kernel, no in-place form
-    const uintptr_t n = uintptr_t(lanes) * frames, xb = reinterpret_cast<uintptr_t>(x), lb = reinterpret_cast<uintptr_t>(lo),
-                    yb = reinterpret_cast<uintptr_t>(y);
-    auto meet = [](uintptr_t a, uintptr_t an, uintptr_t b, uintptr_t bn) { return a < b + bn && b < a + an; };
-    if (n && (meet(xb, n * 4, yb, n * 8) || meet(lb, n * 8, yb, n * 8) || meet(xb, n * 4, lb, n * 8)))
-        return fail(IDSP_EINVAL, "x, lo and y must not overlap");
+    const size_t xb = span_bytes(lanes, frames, 4), cb = span_bytes(lanes, frames, 8);
+    if (ranges_overlap(x, xb, y, cb) || ranges_overlap(lo, cb, y, cb) || ranges_overlap(x, xb, lo, cb)) return fail(IDSP_EINVAL, "x, lo and y must not overlap");
     return IDSP_OK;
 }
 
+inline XWalk x_walk(const void *x, int layout, size_t frames, size_t pitch) { return XWalk{x, layout == IDSP_FRAME_MAJOR ? 1u : 0u, pitch ? pitch : frames}; }
+
 template <int NS>
-int run_biquad_phase(const idsp_biquad_i32 *sec, void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout, hipStream_t s,
-                     size_t pitch = 0)
+int run_biquad_phase(const idsp_biquad_i32 *sec, void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout, hipStream_t s, size_t pitch)
 {
     typename LockinBiquadProc<NS>::Params p;
-    fill_i32<NS>(sec, p.sec);
+    bq::fill_sections(bq::FillI32{sec}, p.sec);
     return launch_stream<LockinBiquadProc<NS>>(p, state, x, reinterpret_cast<Cplx *>(y), lanes, frames, layout, s, Pitch{pitch, pitch});
 }
-template <int NS>
-int run_biquad_lo_i32(const idsp_biquad_i32 *sec, void *state, const int32_t *x, const int32_t *lo, int32_t *y, size_t lanes, size_t frames,
-                      int layout, hipStream_t s, size_t pitch = 0)
+// Sec = Df1I32<false> with FillI32 and T = int32_t, or Df1F32<false> with FillF32 and T = float
+template <class Sec, int NS, class Fill, class T>
+int run_biquad_lo(const Fill &fill, void *state, const T *x, const T *lo, T *y, size_t lanes, size_t frames, int layout, hipStream_t s, size_t pitch)
 {
-    using P = LockinBiquadLoProc<bq::Df1I32<false>, NS>;
+    using P = LockinBiquadLoProc<Sec, NS>;
     typename P::Params p;
-    fill_i32<NS>(sec, p.sec);
-    p.xw = XWalk{x, layout == IDSP_FRAME_MAJOR ? 1u : 0u, pitch ? pitch : frames};
+    bq::fill_sections(fill, p.sec);
+    p.xw = x_walk(x, layout, frames, pitch);
     return launch_stream<P>(p, state, reinterpret_cast<const typename P::In *>(lo), reinterpret_cast<typename P::Out *>(y), lanes, frames, layout, s,
                             Pitch{pitch, pitch});
 }
-template <int NS>
-int run_biquad_lo_f32(const idsp_biquad_f32 *sec, void *state, const float *x, const float *lo, float *y, size_t lanes, size_t frames, int layout,
-                      hipStream_t s, size_t pitch = 0)
+
+// The three external-LO entries behind their checks.  `waves(plan, pitch)` runs the multi-wave kernel on `plan.body` frames,
+// `stream(x, lo, y, frames, pitch)` the stream kernel — on the whole call, or on the last frames % 16 of every LaneMajor row at the
+// call's row pitch (same stream; its launch leaves its own name in idsp_last_kernel()).
+template <class T, class Waves, class Stream>
+int lockin_lo(LockinArms arms, int order, int cascade, const T *x, const T *lo, T *y, size_t lanes, size_t frames, int layout, Waves waves, Stream stream)
 {
-    using P = LockinBiquadLoProc<bq::Df1F32<false>, NS>;
-    typename P::Params p;
-    fill_f32<NS>(sec, p.sec);
-    p.xw = XWalk{x, layout == IDSP_FRAME_MAJOR ? 1u : 0u, pitch ? pitch : frames};
-    return launch_stream<P>(p, state, reinterpret_cast<const typename P::In *>(lo), reinterpret_cast<typename P::Out *>(y), lanes, frames, layout, s, Pitch{pitch, pitch});
+    const LockinPlan plan = lockin_plan_for(arms, LockinLo::Buffer, MODE_IQ, order, cascade, x, y, lanes, frames, layout);
+    size_t pitch = 0;
+    if (plan.form != LockinForm::Stream) {
+        const bool tail = plan.form == LockinForm::WavesTail;
+        const int rc = waves(plan, tail ? frames : 0);
+        if (rc || !tail) return rc;
+        pitch = frames, x += plan.body, lo += 2 * plan.body, y += 2 * plan.body, frames -= plan.body;
+    }
+    return stream(x, lo, y, frames, pitch);
+}
+
+template <class Sec, class Fill, class S, class T, class Waves>
+int lockin_biquad_lo(Waves waves, const S *sections, size_t n, void *state, const T *x, const T *lo, T *y, size_t lanes, size_t frames, int layout, void *stream)
+{
+    const hipStream_t s = as_stream(stream);
+    return lockin_lo(
+        LockinArms::Biquad, 0, 0, x, lo, y, lanes, frames, layout,
+        [&](const LockinPlan &plan, size_t pitch) { return waves(sections, n, state, x, lo, y, lanes, plan, s, pitch); },
+        [&](const T *xs, const T *los, T *ys, size_t fr, size_t pitch) {
+            return for_sections(n, [&](auto ns) { return run_biquad_lo<Sec, decltype(ns)::value>(Fill{sections}, state, xs, los, ys, lanes, fr, layout, s, pitch); });
+        });
 }
 
 }  // namespace
@@ -296,14 +263,6 @@ size_t idsp_lockin_biquad_state_words(size_t n, int with_accu)
     return n >= 1 && n <= IDSP_LOCKIN_MAX_SECTIONS ? size_t(with_accu ? 2 : 0) + 8 * n : 0;
 }
 
-#define IDSP_BY_SECTIONS(call)                                     \
-    switch (n) {                                                   \
-        case 1: return call(1);                                    \
-        case 2: return call(2);                                    \
-        case 3: return call(3);                                    \
-        default: return call(4);                                   \
-    }
-
 int idsp_lockin_i32_biquad_process(const idsp_biquad_i32 *sections, size_t n, void *state, const int32_t *x, int32_t *y, size_t lanes,
                                    size_t frames, int layout, void *stream)
 {
@@ -313,53 +272,40 @@ int idsp_lockin_i32_biquad_process(const idsp_biquad_i32 *sections, size_t n, vo
     for (size_t k = 0; k < n; k++)
         if (sections[k].frac < 0 || sections[k].frac > 31) return fail(IDSP_EINVAL, "section %zu: frac = %d not in 0..31", k, sections[k].frac);
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    if (waves_take(x, y, lanes, frames, layout)) return lockin_waves_biquad_iq(sections, n, state, x, y, lanes, frames, layout, as_stream(stream));
-    // LaneMajor rows of 32 + 4 k frames that are not whole batches: the whole batches of every row on the multi-wave kernel at the call's row
-    // pitch, the last frames % 16 on the stream kernel behind it (as for the lowpass arms, dds.hip lockin_lm_body)
-    if (const size_t body = lm_body(x, y, lanes, frames, layout)) {
-        if ((rc = lockin_waves_biquad_iq(sections, n, state, x, y, lanes, body, layout, as_stream(stream), frames))) return rc;
-#define IDSP_CALL(NS) run_biquad_phase<NS>(sections, state, x + body, y + 2 * body, lanes, frames - body, layout, as_stream(stream), frames)
-        rc = [&]() -> int { IDSP_BY_SECTIONS(IDSP_CALL) }();
-#undef IDSP_CALL
-        if (rc == IDSP_OK) note_kernel("lockin_waves_kernel + stream kernel (last frames % 16)", "[Biquad; n]");
-        return rc;
-    }
-#define IDSP_CALL(NS) run_biquad_phase<NS>(sections, state, x, y, lanes, frames, layout, as_stream(stream))
-    IDSP_BY_SECTIONS(IDSP_CALL)
-#undef IDSP_CALL
+    const hipStream_t s = as_stream(stream);
+    const auto on_stream = [&](const int32_t *xs, int32_t *ys, size_t fr, size_t pitch) {
+        return for_sections(n, [&](auto ns) { return run_biquad_phase<decltype(ns)::value>(sections, state, xs, ys, lanes, fr, layout, s, pitch); });
+    };
+    const LockinPlan plan = lockin_plan_for(LockinArms::Biquad, LockinLo::Phase, MODE_IQ, 0, 0, x, y, lanes, frames, layout);
+    if (plan.form == LockinForm::Stream) return on_stream(x, y, frames, 0);
+    // WavesTail: the whole batches of every LaneMajor row on the multi-wave kernel at the call's row pitch, the last frames % 16 on the
+    // stream kernel behind it (as for the lowpass arms, dds.hip)
+    const bool tail = plan.form == LockinForm::WavesTail;
+    rc = lockin_waves_biquad_iq(sections, n, state, x, y, lanes, plan, s, tail ? frames : 0);
+    if (rc || !tail) return rc;
+    rc = on_stream(x + plan.body, y + 2 * plan.body, frames - plan.body, frames);
+    if (rc == IDSP_OK) note_kernel(lockin_plan_name(plan), "[Biquad; n]");
+    return rc;
 }
 
 int idsp_lockin_i32_lo_process(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, const int32_t *lo, int32_t *y, size_t lanes,
                                size_t frames, int layout, void *stream)
 {
-    if (!cfg || (cfg->order != 1 && cfg->order != 2) || cfg->cascade < 1 || cfg->cascade > IDSP_LOCKIN_MAX_CASCADE)
-        return fail(IDSP_EINVAL, "lock-in configuration: order 1..2, cascade 1..%d", IDSP_LOCKIN_MAX_CASCADE);
-    int rc = check_lo_args(cfg, state, x, lo, y, lanes, frames, layout);
+    int rc = lockin_cfg_check(cfg);
     if (rc) return rc;
+    if ((rc = check_lo_args(cfg, state, x, lo, y, lanes, frames, layout))) return rc;
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    if (waves_take(x, y, lanes, frames, layout)) return lockin_waves_lowpass_lo(cfg, state, x, lo, y, lanes, frames, layout, as_stream(stream));
-    size_t pitch = 0;
-    if (const size_t body = lm_body(x, y, lanes, frames, layout)) {
-        if ((rc = lockin_waves_lowpass_lo(cfg, state, x, lo, y, lanes, body, layout, as_stream(stream), frames))) return rc;
-        pitch = frames, x += body, lo += 2 * body, y += 2 * body, frames -= body;
-    }
-    LpLoParams p;
-    p.lp = lp_params(cfg);
-    p.xw = XWalk{x, layout == IDSP_FRAME_MAJOR ? 1u : 0u, pitch ? pitch : frames};
-    const cplx_i32 *l2 = reinterpret_cast<const cplx_i32 *>(lo);
-    Cplx *y2 = reinterpret_cast<Cplx *>(y);
-#define IDSP_CASE(N, K) \
-    if (cfg->order == N && cfg->cascade == K) return launch_stream<LockinLoProc<N, K>>(p, state, l2, y2, lanes, frames, layout, as_stream(stream), Pitch{pitch, pitch})
-    IDSP_CASE(1, 1);
-    IDSP_CASE(1, 2);
-    IDSP_CASE(1, 3);
-    IDSP_CASE(1, 4);
-    IDSP_CASE(2, 1);
-    IDSP_CASE(2, 2);
-    IDSP_CASE(2, 3);
-    IDSP_CASE(2, 4);
-#undef IDSP_CASE
-    return fail(IDSP_EINVAL, "unsupported lowpass configuration");
+    const hipStream_t s = as_stream(stream);
+    return lockin_lo(
+        LockinArms::Lowpass, cfg->order, cfg->cascade, x, lo, y, lanes, frames, layout,
+        [&](const LockinPlan &plan, size_t pitch) { return lockin_waves_lowpass_lo(cfg, state, x, lo, y, lanes, plan, s, pitch); },
+        [&](const int32_t *xs, const int32_t *los, int32_t *ys, size_t fr, size_t pitch) {
+            const LpLoParams p{lp_params(cfg), x_walk(xs, layout, fr, pitch)};
+            return for_nk(cfg, [&](auto nn, auto k) {
+                return launch_stream<LockinLoProc<decltype(nn)::value, decltype(k)::value>>(p, state, reinterpret_cast<const cplx_i32 *>(los), reinterpret_cast<Cplx *>(ys),
+                                                                                           lanes, fr, layout, s, Pitch{pitch, pitch});
+            });
+        });
 }
 
 int idsp_lockin_i32_biquad_lo_process(const idsp_biquad_i32 *sections, size_t n, void *state, const int32_t *x, const int32_t *lo, int32_t *y,
@@ -371,15 +317,7 @@ int idsp_lockin_i32_biquad_lo_process(const idsp_biquad_i32 *sections, size_t n,
     for (size_t k = 0; k < n; k++)
         if (sections[k].frac < 0 || sections[k].frac > 31) return fail(IDSP_EINVAL, "section %zu: frac = %d not in 0..31", k, sections[k].frac);
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    if (waves_take(x, y, lanes, frames, layout)) return lockin_waves_biquad_lo(sections, n, state, x, lo, y, lanes, frames, layout, as_stream(stream));
-    size_t pitch = 0;
-    if (const size_t body = lm_body(x, y, lanes, frames, layout)) {
-        if ((rc = lockin_waves_biquad_lo(sections, n, state, x, lo, y, lanes, body, layout, as_stream(stream), frames))) return rc;
-        pitch = frames, x += body, lo += 2 * body, y += 2 * body, frames -= body;
-    }
-#define IDSP_CALL(NS) run_biquad_lo_i32<NS>(sections, state, x, lo, y, lanes, frames, layout, as_stream(stream), pitch)
-    IDSP_BY_SECTIONS(IDSP_CALL)
-#undef IDSP_CALL
+    return lockin_biquad_lo<bq::Df1I32<false>, bq::FillI32>(lockin_waves_biquad_lo, sections, n, state, x, lo, y, lanes, frames, layout, stream);
 }
 
 int idsp_lockin_f32_biquad_lo_process(const idsp_biquad_f32 *sections, size_t n, void *state, const float *x, const float *lo, float *y,
@@ -389,15 +327,7 @@ int idsp_lockin_f32_biquad_lo_process(const idsp_biquad_f32 *sections, size_t n,
     int rc = check_lo_args(sections, state, x, lo, y, lanes, frames, layout);
     if (rc) return rc;
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    if (waves_take(x, y, lanes, frames, layout)) return lockin_waves_biquad_lo_f32(sections, n, state, x, lo, y, lanes, frames, layout, as_stream(stream));
-    size_t pitch = 0;
-    if (const size_t body = lm_body(x, y, lanes, frames, layout)) {
-        if ((rc = lockin_waves_biquad_lo_f32(sections, n, state, x, lo, y, lanes, body, layout, as_stream(stream), frames))) return rc;
-        pitch = frames, x += body, lo += 2 * body, y += 2 * body, frames -= body;
-    }
-#define IDSP_CALL(NS) run_biquad_lo_f32<NS>(sections, state, x, lo, y, lanes, frames, layout, as_stream(stream), pitch)
-    IDSP_BY_SECTIONS(IDSP_CALL)
-#undef IDSP_CALL
+    return lockin_biquad_lo<bq::Df1F32<false>, bq::FillF32>(lockin_waves_biquad_lo_f32, sections, n, state, x, lo, y, lanes, frames, layout, stream);
 }
 
 }  // extern "C"

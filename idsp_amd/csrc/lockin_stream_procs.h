@@ -197,18 +197,9 @@ int dispatch_nk(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, OutT 
 {
     // pitch (LaneMajor): elements between the rows of x and of y, 0 = dense
     const LpParams p = lp_params(cfg);
-#define IDSP_CASE(N, K) \
-    if (cfg->order == N && cfg->cascade == K) return launch_stream<Proc<N, K>>(p, state, x, y, lanes, frames, layout, s, Pitch{pitch, pitch})
-    IDSP_CASE(1, 1);
-    IDSP_CASE(1, 2);
-    IDSP_CASE(1, 3);
-    IDSP_CASE(1, 4);
-    IDSP_CASE(2, 1);
-    IDSP_CASE(2, 2);
-    IDSP_CASE(2, 3);
-    IDSP_CASE(2, 4);
-#undef IDSP_CASE
-    return fail(IDSP_EINVAL, "unsupported lowpass configuration");
+    return for_nk(cfg, [&](auto n, auto k) {
+        return launch_stream<Proc<decltype(n)::value, decltype(k)::value>>(p, state, x, y, lanes, frames, layout, s, Pitch{pitch, pitch});
+    });
 }
 
 }  // namespace

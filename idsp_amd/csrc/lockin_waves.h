@@ -27,10 +27,7 @@
 namespace idsp {
 namespace {
 
-constexpr int kLwB = 8;     // frames per batch, FrameMajor
-constexpr int kLwBLm = 16;  // LaneMajor: 16 frames = one whole 128-byte line of 8-byte output elements per lane and batch
-enum { MODE_IQ = 0, MODE_ARG = 1, MODE_NORM_SQR = 2 };
-enum { IN_FM_REG = 0, IN_FM_DMA = 1, IN_LM_REG = 2, IN_LM_DMA = 3 };
+// (kLwB, kLwBLm, MODE_*, IN_*: lockin_plan.h, which decides them)
 // LaneMajor DMA: ring slots of one PAIR of batches (8 KiB) each, pairs requested ahead.  Three slots keep the workgroup at
 // 70 KiB of LDS, so that two of them share a CU (four slots: 78 KiB, measured slower: 0.457 against 0.42-0.44 ms at C4)
 constexpr int kLwRing = 3, kLwAhead = 2;
@@ -49,8 +46,7 @@ constexpr int kLwPieceGroup = 1;                 // the 16-byte-piece form
 // q of their rows at the same time.  A start-up stagger over the CUs of an XCD — workgroup b waits ((b >> 4) % 4) steps of
 // `skew` ticks (10 ns each; workgroup b runs on XCD b % 8) — buys more than it costs: 0.357 -> 0.328-0.335 ms at C4 for steps of
 // 5-13 us and moduli 3-8, including the 15-40 us the last group waits (shifts 0-2 and 6-8, i.e. phases per XCD or per
-// workgroup pair, gain nothing).  Which launches: launch_lockin_waves_in.
-constexpr unsigned kLwSkewTicks = thr::kLockinStaggerTicks;
+// workgroup pair, gain nothing).  Which launches, and thr::kLockinStaggerTicks: plan_lockin.
 #ifndef IDSP_LW_LM_LINES
 #define IDSP_LW_LM_LINES 1  // LaneMajor, 8-byte elements: whole 128-byte lines per store instruction
 #endif
@@ -655,7 +651,7 @@ __global__ __launch_bounds__(W * kWave) __attribute__((amdgpu_waves_per_eu(1, IN
 #ifndef IDSP_LS_RING
 #define IDSP_LS_RING 5
 #endif
-constexpr int kLsB = 16, kLsRing = IDSP_LS_RING, kLsAhead = IDSP_LS_RING - 1;  // input ring slots / batches requested ahead
+constexpr int kLsRing = IDSP_LS_RING, kLsAhead = IDSP_LS_RING - 1;  // input ring slots / batches requested ahead (kLsB: lockin_plan.h)
 
 template <int N, int MODE, int G, int R = 2>
 __global__ __launch_bounds__((4 + R) * G *kWave) void lockin_stages_kernel(const LpParams prm, uint32_t *st, const int32_t *x,
@@ -799,134 +795,80 @@ __global__ __launch_bounds__((4 + R) * G *kWave) void lockin_stages_kernel(const
     }
 }
 
-// Which launches the stage-wave kernel takes (0 = none, else lane groups per workgroup): whole 64-lane groups, whole batches,
-// aligned rows, K = 2.  Measured at 4096 frames against the 4- / 6-wave kernel with the same table cossin and roles by SIMD
+// Which launches the stage-wave kernel takes (plan_lockin, LockinForm::Stages): whole 64-lane groups, whole batches, aligned rows,
+// K = 2.  Measured at 4096 frames against the 4- / 6-wave kernel with the same table cossin and roles by SIMD
 // (tools/exp_lockin_stages.hip, profiles/r03_exp_lockin_stages*.jsonl): `Complex<i32>` / `norm_sqr` read-out 0.207 against 0.232 ms
 // up to 16384 lanes (one workgroup per CU or fewer: eight waves per 64 lanes instead of four) but 0.345 against 0.317 at 32768 and
 // 0.64 against 0.57 at 49152, so those take it up to 16384 lanes; the `arg` read-out (atan2 on the read-out waves) 0.337 / 0.465 /
 // 0.93 against 0.384 / 0.51 / 1.16 ms at 16384 / 32768 / 65536 lanes (16-byte table entries: 0.311 against 0.289 of the HBM peak from 65536 to
 // 196608 lanes), so it takes it at every lane count.
 // IDSP_DIAG switches: IDSP_LOCKIN_NO_STAGES=1 never, IDSP_LOCKIN_STAGE_GROUPS=1 / 2 always (when the shape allows).
-inline int lockin_stage_groups(const void *x, size_t lanes, size_t frames, int layout, int cascade, bool heavy_readout)
-{
-    static const bool off = diag_env("IDSP_LOCKIN_NO_STAGES") != nullptr;
-    static const int forced = [] {
-        const char *e = diag_env("IDSP_LOCKIN_STAGE_GROUPS");
-        return e ? atoi(e) : 0;
-    }();
-    if (off || layout != IDSP_FRAME_MAJOR || cascade != 2 || frames == 0 || frames % kLsB != 0 || lanes == 0 || lanes % kWave != 0 ||
-        reinterpret_cast<uintptr_t>(x) % 16 != 0)
-        return 0;
-    const bool pairs = lanes % (2 * kWave) == 0;
-    if (forced == 1 || (forced == 2 && pairs)) return forced;
-    if (lanes <= 16384) return 1;
-    return heavy_readout && pairs ? 2 : 0;
-}
+static_assert(kPlanWave == size_t(kWave), "lockin_plan.h counts workgroups of this many lanes");
 
+// The launchers below only switch on the plan (lockin_plan.h) into the kernel it names; `plan.body` is the frame count.
 template <int MODE, int N>
-int launch_lockin_stages(const LpParams &p, void *state, const int32_t *x, void *yv, size_t lanes, size_t frames, int groups, hipStream_t s)
+int launch_lockin_stages(const LpParams &p, void *state, const int32_t *x, void *yv, size_t lanes, const LockinPlan &plan, hipStream_t s)
 {
     using Out = typename LwOut<MODE>::type;
     uint32_t *st = static_cast<uint32_t *>(state);
     Out *y = static_cast<Out *>(yv);
-    if (groups == 2) {
-        note_kernel("lockin_stages_kernel[16 waves per 128 lanes]");
-        hipLaunchKernelGGL((lockin_stages_kernel<N, MODE, 2, 4>), dim3(unsigned(lanes / (2 * kWave))), dim3(16 * kWave), 0, s, p, st, x, y, lanes, frames);
-    } else {
-        note_kernel("lockin_stages_kernel[8 waves per 64 lanes]");
-        hipLaunchKernelGGL((lockin_stages_kernel<N, MODE, 1, 4>), dim3(unsigned(lanes / kWave)), dim3(8 * kWave), 0, s, p, st, x, y, lanes, frames);
-    }
+    note_kernel(lockin_plan_name(plan));
+    if (plan.groups == 2)
+        hipLaunchKernelGGL((lockin_stages_kernel<N, MODE, 2, 4>), dim3(unsigned(lanes / (2 * kWave))), dim3(16 * kWave), 0, s, p, st, x, y, lanes, plan.body);
+    else
+        hipLaunchKernelGGL((lockin_stages_kernel<N, MODE, 1, 4>), dim3(unsigned(lanes / kWave)), dim3(8 * kWave), 0, s, p, st, x, y, lanes, plan.body);
     return launch_status();
 }
 
 template <int MODE, class Bank, int IN, int B>
 int launch_lockin_waves_in(const typename Bank::Params &p, uint32_t *st, const int32_t *x, typename LwOut<MODE>::type *y, size_t lanes,
-                           size_t frames, int waves, hipStream_t s, const int32_t *lo, size_t pitch)
+                           const LockinPlan &plan, hipStream_t s, const int32_t *lo, size_t pitch)
 {
     const dim3 grid(unsigned((lanes + kWave - 1) / kWave));
+    const size_t frames = plan.body;
     if (pitch == 0) pitch = frames;
-    // start-up stagger (see kLwSkewTicks): LaneMajor launches that fill the chip, long enough for the wait to pay
-    // (IDSP_DIAG=1 IDSP_LOCKIN_NO_SKEW=1: none)
-    static const bool no_skew = diag_env("IDSP_LOCKIN_NO_SKEW") != nullptr;
-    // (one workgroup per CU: 16384 x 4096 0.217 -> 0.225 ms with it; 32768 lanes x 2048 frames 0.187 -> 0.179, x 4096 0.350 -> 0.323,
-    // x 16384 1.335 -> 1.358: long calls drift apart by themselves; 65536 x 4096 0.696 -> 0.640)
-    const unsigned skew = (IN == IN_LM_REG || IN == IN_LM_DMA) && !no_skew && grid.x >= thr::kStaggerMinWorkgroups && frames >= thr::kStaggerMinFrames && frames <= thr::kStaggerMaxFrames && stagger_tuned_device() ? kLwSkewTicks : 0u;
-    note_kernel(waves == 6 ? "lockin_waves_kernel[6 waves per 64 lanes]" : "lockin_waves_kernel[4 waves per 64 lanes]", Bank::name());
+    note_kernel(lockin_waves_name(plan.waves), Bank::name());
     if constexpr (Bank::kSixWaves) {
-        if (waves == 6) {
-            hipLaunchKernelGGL((lockin_waves_kernel<Bank, 6, IN, MODE, B>), grid, dim3(6 * kWave), 0, s, p, st, x, y, lanes, frames, lo, skew, pitch);
+        if (plan.waves == 6) {
+            hipLaunchKernelGGL((lockin_waves_kernel<Bank, 6, IN, MODE, B>), grid, dim3(6 * kWave), 0, s, p, st, x, y, lanes, frames, lo, plan.skew, pitch);
             return launch_status();
         }
     }
-    hipLaunchKernelGGL((lockin_waves_kernel<Bank, 4, IN, MODE, B>), grid, dim3(4 * kWave), 0, s, p, st, x, y, lanes, frames, lo, skew, pitch);
+    hipLaunchKernelGGL((lockin_waves_kernel<Bank, 4, IN, MODE, B>), grid, dim3(4 * kWave), 0, s, p, st, x, y, lanes, frames, lo, plan.skew, pitch);
     return launch_status();
 }
 
-// batch length and input form for a bank on the multi-wave kernel (`waves` from lockin_waves_for, dds.hip)
+// input form and batch length of a bank on the multi-wave kernel (16-frame batches: the FrameMajor DMA form alone)
 template <int MODE, class Bank>
 int launch_lockin_waves_bank(const typename Bank::Params &p, uint32_t *st, const int32_t *x, typename LwOut<MODE>::type *y, size_t lanes,
-                             size_t frames, int layout, int waves, hipStream_t s, const int32_t *lo = nullptr, size_t pitch = 0)
+                             const LockinPlan &plan, hipStream_t s, const int32_t *lo = nullptr, size_t pitch = 0)
 {
-    static const bool no_dma = diag_env("IDSP_LOCKIN_NO_DMA") != nullptr;
-    // 16-frame batches halve the barriers per frame: 0.37 -> 0.35 ms (Complex<i32>), 0.61 -> 0.59 ms (arg) at 32768 lanes x 4096
-    // frames, but 1.06 -> 1.19 ms (arg) at 65536 lanes, where the longer intervals cost more than the barriers
-    // (IDSP_LOCKIN_B = 8 / 16 forces one)
-    static const int forced_b = [] {
-        const char *e = diag_env("IDSP_LOCKIN_B");
-        return e ? atoi(e) : 0;
-    }();
-    // the 6-wave form keeps 8-frame batches: with 16 (66 KiB of LDS) only ONE 6-wave workgroup runs on a CU at a time — every
-    // second workgroup started after the first had finished (tools/exp_lockin_trace.hip) although the occupancy API promises two
-    // Four workgroups per CU (49152 < lanes <= 65536) also take 16-frame batches: two co-resident workgroups in two rounds, where the 8-frame
-    // form's three leave a round of one (0.649 against 0.581 of the HBM peak at 65536 lanes; 49152: 0.557 against 0.654, 98304: 0.649 against 0.666,
-    // profiles/r03_exp_lockin_batch_v2.jsonl)
-    const bool b16 = forced_b == 16 || (forced_b != 8 && ((waves == 4 && (lanes <= kSplitMaxLanes || (lanes > 49152 && lanes <= 65536))) ||
-                                                          (waves == 6 && lanes <= 16384)));  // six waves, one workgroup per CU: dds.hip lockin_waves_for
-    if (layout == IDSP_LANE_MAJOR) {
-        // input by DMA (whole 128-byte lines, each requested once) for the 4-wave I/Q and norm_sqr forms: 0.48 -> 0.43-0.44 ms
-        // at 32768 lanes x 4096 frames, 0.94 -> 0.86 at 65536; its 32 KiB ring halves the workgroups a CU can hold, which
-        // costs the 6-wave form and the arg read-out more than the input gains (tools/exp_lockin_lm.py)
-        if (!no_dma && waves == 4 && MODE != MODE_ARG)
-            return launch_lockin_waves_in<MODE, Bank, IN_LM_DMA, kLwBLm>(p, st, x, y, lanes, frames, waves, s, lo, pitch);
-        return launch_lockin_waves_in<MODE, Bank, IN_LM_REG, kLwBLm>(p, st, x, y, lanes, frames, waves, s, lo, pitch);
+    switch (plan.in) {
+        case IN_LM_DMA: return launch_lockin_waves_in<MODE, Bank, IN_LM_DMA, kLwBLm>(p, st, x, y, lanes, plan, s, lo, pitch);
+        case IN_LM_REG: return launch_lockin_waves_in<MODE, Bank, IN_LM_REG, kLwBLm>(p, st, x, y, lanes, plan, s, lo, pitch);
+        case IN_FM_DMA:
+            if (plan.batch == 16) return launch_lockin_waves_in<MODE, Bank, IN_FM_DMA, 16>(p, st, x, y, lanes, plan, s, lo, pitch);
+            return launch_lockin_waves_in<MODE, Bank, IN_FM_DMA, kLwB>(p, st, x, y, lanes, plan, s, lo, pitch);
+        default: return launch_lockin_waves_in<MODE, Bank, IN_FM_REG, kLwB>(p, st, x, y, lanes, plan, s, lo, pitch);
     }
-    if (!no_dma && lanes % kWave == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0) {
-        if (b16) return launch_lockin_waves_in<MODE, Bank, IN_FM_DMA, 16>(p, st, x, y, lanes, frames, waves, s, lo, pitch);
-        return launch_lockin_waves_in<MODE, Bank, IN_FM_DMA, kLwB>(p, st, x, y, lanes, frames, waves, s, lo, pitch);
-    }
-    return launch_lockin_waves_in<MODE, Bank, IN_FM_REG, kLwB>(p, st, x, y, lanes, frames, waves, s, lo, pitch);
 }
 
-template <int MODE, int N, int K>
-int launch_lockin_waves_nk(const LpParams &p, void *state, const int32_t *x, void *yv, size_t lanes, size_t frames, int layout,
-                           int waves, hipStream_t s, size_t pitch)
-{
-    using Out = typename LwOut<MODE>::type;
-    if constexpr (K == 2) {
-        if (const int groups = lockin_stage_groups(x, lanes, frames, layout, K, MODE == MODE_ARG))
-            return launch_lockin_stages<MODE, N>(p, state, x, yv, lanes, frames, groups, s);
-    }
-    return launch_lockin_waves_bank<MODE, LpBank<N, K>>(p, static_cast<uint32_t *>(state), x, static_cast<Out *>(yv), lanes, frames, layout, waves, s, nullptr, pitch);
-}
-
+// the three phase-form entries with lowpass arms (lockin_waves_{iq,arg,norm_sqr}.hip)
 template <int MODE>
-int launch_lockin_waves(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, void *y, size_t lanes, size_t frames, int layout,
-                        int waves, hipStream_t s, size_t pitch = 0)
+int launch_lockin_waves(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, void *y, size_t lanes, const LockinPlan &plan, hipStream_t s,
+                        size_t pitch)
 {
     const LpParams p = lp_params(cfg);
-#define IDSP_CASE(N, K) \
-    if (cfg->order == N && cfg->cascade == K) return launch_lockin_waves_nk<MODE, N, K>(p, state, x, y, lanes, frames, layout, waves, s, pitch)
-    IDSP_CASE(1, 1);
-    IDSP_CASE(1, 2);
-    IDSP_CASE(1, 3);
-    IDSP_CASE(1, 4);
-    IDSP_CASE(2, 1);
-    IDSP_CASE(2, 2);
-    IDSP_CASE(2, 3);
-    IDSP_CASE(2, 4);
-#undef IDSP_CASE
-    return fail(IDSP_EINVAL, "unsupported lowpass configuration");
+    return for_nk(cfg, [&](auto n, auto k) {
+        constexpr int N = decltype(n)::value, K = decltype(k)::value;
+        if constexpr (K == 2) {
+            if (plan.form == LockinForm::Stages) return launch_lockin_stages<MODE, N>(p, state, x, y, lanes, plan, s);
+        }
+        return launch_lockin_waves_bank<MODE, LpBank<N, K>>(p, static_cast<uint32_t *>(state), x, static_cast<typename LwOut<MODE>::type *>(y), lanes, plan, s,
+                                                            nullptr, pitch);
+    });
 }
 
 }  // namespace
 }  // namespace idsp
+

@@ -4,10 +4,10 @@
 
 namespace idsp {
 
-int lockin_waves_norm_sqr(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, void *y, size_t lanes, size_t frames, int layout,
-                         int waves, hipStream_t s, size_t pitch)
+int lockin_waves_norm_sqr(const idsp_lockin_i32 *cfg, void *state, const int32_t *x, void *y, size_t lanes, const LockinPlan &plan, hipStream_t s,
+    size_t pitch)
 {
-    return launch_lockin_waves<MODE_NORM_SQR>(cfg, state, x, y, lanes, frames, layout, waves, s, pitch);
+    return launch_lockin_waves<MODE_NORM_SQR>(cfg, state, x, y, lanes, plan, s, pitch);
 }
 
 }  // namespace idsp

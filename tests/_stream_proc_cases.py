@@ -68,6 +68,10 @@ NOT_CONSULTED = {
     "kDuoMinLanes": "two-wave chain kernel: biquad chains only", "kDuo4MaxLanes": "two-wave chain kernel: biquad chains only",
     "kStaggerMinWorkgroups": "lockin_waves.h / dds.hip", "kStaggerMinFrames": "lockin_waves.h / dds.hip",
     "kStaggerMaxFrames": "lockin_waves.h / dds.hip", "kLockinStaggerTicks": "lockin_waves.h", "kFmDiscStaggerTicks": "dds.hip",
+    # the lock-in entries' own dispatch: tests/_lockin_plan_cases.py holds a row on each side of every one of them
+    "kSplitMaxLanes": "lockin_plan.h", "kLockinSixWavesMaxLanes": "lockin_plan.h", "kLockinStagesOneGroupMaxLanes": "lockin_plan.h",
+    "kLockinSixWavesArmWeight": "lockin_plan.h", "kLockinB16MinLanes": "lockin_plan.h", "kLockinB16MaxLanes": "lockin_plan.h",
+    "kLockinWavesMaxLanes": "lockin_plan.h", "kLockinTailMinFrames": "lockin_plan.h",
     # compared as the plain constants above, not through _cmp: tests/test_stream_proc_cases.py `minimum()` holds a case on each side of them
     "kHeavyCost": "HEAVY_COST: a compile-time condition on COST", "kFewMaxLanes": "FEW_MAX_LANES", "kFewMinFrames": "FEW_MIN_FRAMES",
     "kOddSplitMinBody": "ODD_MIN_BODY", "kOddSplitMinFrames": "ODD_MIN_FRAMES", "kRoundsSplitMinFrames": "ROUND_MIN_FRAMES",

@@ -7,6 +7,11 @@
 //           0 = dense; a switch counts as set under IDSP_DIAG=1, which therefore has to be among them — exactly as in the library)
 //   geom <lanes> <max_lpt>                     -> `grid x lpt x bw, rounds` of sweep_geometry, or `none`
 //   duo <sections> <lanes> <FM|LM> [IDSP_SWITCH=value ...]  -> 0 / 1 of duo_wanted
+//   lockin <entry> <order | n> <cascade | 0> <lanes> <frames> <FM|LM> <x mod 64> <y mod 64> [tuned] [IDSP_SWITCH=value ...]
+//        -> `plan_lockin` (idsp_amd/csrc/lockin_plan.h) for a call of idsp_lockin_i32_<entry> (process, arg, norm_sqr, biquad_process, lo_process,
+//           biquad_lo_process, accu_process) or idsp_lockin_f32_biquad_lo_process (f32_biquad_lo_process): what idsp_last_kernel() reports —
+//           `stream_<Processor>` where launch_stream names the kernel —, a tab, `waves= groups= batch= in= skew= body= split=`
+//           (tuned: stagger_tuned_device() holds)
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -14,6 +19,7 @@
 #include <sstream>
 #include <string>
 
+#include "../../idsp_amd/csrc/lockin_plan.h"
 #include "../../idsp_amd/csrc/stream_plan.h"
 
 using namespace idsp;
@@ -68,6 +74,44 @@ static void print_plan(const StreamTraits &t, StreamCall c, const StreamSwitches
     detail = text;
 }
 
+// The lock-in entries, by hand: arms and LO of each, the stream processor it runs (dds.hip, lockin_generic.hip, lockin_accu.hip) and the
+// name of its arm functor on the multi-wave kernel (`Bank::name()`: lockin_waves_biquad.hip, lockin_waves_lo.hip; none for `LpBank`)
+static bool lockin_line(std::istringstream &in, const LockinSwitches &sw, bool tuned, const std::string &entry, std::string &out)
+{
+    static const std::map<std::string, int> kEntries = {{"process", 0}, {"arg", 1}, {"norm_sqr", 2}, {"biquad_process", 3}, {"lo_process", 4},
+                                                        {"biquad_lo_process", 5}, {"f32_biquad_lo_process", 6}, {"accu_process", 7}};
+    int a = 0, b = 0;
+    size_t xo = 0, yo = 0;
+    std::string layout;
+    LockinCall c;
+    in >> a >> b >> c.lanes >> c.frames >> layout >> xo >> yo;
+    if (!in || !kEntries.count(entry) || (layout != "FM" && layout != "LM")) return false;
+    const int e = kEntries.at(entry);
+    c.arms = e == 3 || e == 5 || e == 6 ? LockinArms::Biquad : LockinArms::Lowpass;
+    c.lo = e <= 3 ? LockinLo::Phase : e == 7 ? LockinLo::Accu : LockinLo::Buffer;
+    c.readout = e == 1 ? MODE_ARG : e == 2 ? MODE_NORM_SQR : MODE_IQ;
+    if (c.arms == LockinArms::Lowpass) c.order = a, c.cascade = b;
+    c.layout = layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR;
+    c.x = (uintptr_t(1) << 32) + xo, c.y = (uintptr_t(1) << 33) + yo;
+    c.tuned_device = tuned;
+    const LockinPlan p = plan_lockin(c, sw);
+    char proc[96], bank[64] = "", text[512];
+    const char *const procs[8] = {p.split ? "LockinSplitProc<%d, %d>" : "LockinProc<%d, %d>", "LockinPolarProc<%d, %d, 0>", "LockinPolarProc<%d, %d, 1>", "LockinBiquadProc<%d>",
+                                  "LockinLoProc<%d, %d>", "LockinBiquadLoProc<idsp::bq::Df1I32<false>, %d>", "LockinBiquadLoProc<idsp::bq::Df1F32<false>, %d>",
+                                  p.split ? "LockinAccuSplitProc<%d, %d>" : "LockinAccuProc<%d, %d>"};
+    const char *const banks[8] = {"", "", "", "[Biquad; %d]", "[Lowpass<N>; K], LO", "[Biquad; %d], LO", "[Biquad<f32>; %d], LO", ""};
+    snprintf(proc, sizeof proc, procs[e], a, b);
+    snprintf(bank, sizeof bank, banks[e], a);
+    // the entries with an LO buffer leave the name of the tail's stream launch; the biquad phase entry records the combined one with "[Biquad; n]"
+    const bool streams = p.form == LockinForm::Stream || (p.form == LockinForm::WavesTail && c.lo == LockinLo::Buffer);
+    const char *detail = streams ? proc : p.form == LockinForm::Waves ? bank : p.form == LockinForm::WavesTail && e == 3 ? "[Biquad; n]" : "";
+    static const char *const kIn[5] = {"-", "FM_REG", "FM_DMA", "LM_REG", "LM_DMA"};
+    snprintf(text, sizeof text, "%s%s%s%s\twaves=%d groups=%d batch=%d in=%s skew=%u body=%zu split=%d", streams ? "stream_" : lockin_plan_name(p), *detail ? "<" : "", detail,
+             *detail ? ">" : "", p.waves, p.groups, p.batch, kIn[p.in + 1], p.skew, p.body, int(p.split));
+    out = text;
+    return true;
+}
+
 int main()
 {
     std::string line;
@@ -97,6 +141,26 @@ int main()
             in >> m >> lanes >> layout;
             while (in >> word) env[word.substr(0, word.find('='))] = word.find('=') == std::string::npos ? "" : word.substr(word.find('=') + 1);
             printf("%d\n", int(duo_wanted(m, lanes, layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR, read_stream_switches(getenv_))));
+        } else if (cmd == "lockin") {
+            std::string entry, rest, out;
+            in >> entry;
+            std::getline(in, rest);
+            bool tuned = false;
+            std::string shape;
+            std::istringstream words(rest);
+            while (words >> word) {
+                if (word == "tuned")
+                    tuned = true;
+                else if (word.find('=') != std::string::npos)
+                    env[word.substr(0, word.find('='))] = word.substr(word.find('=') + 1);
+                else
+                    shape += word + " ";
+            }
+            std::istringstream shape_in(shape);
+            if (lockin_line(shape_in, read_lockin_switches(getenv_), tuned, entry, out))
+                printf("%s\n", out.c_str());
+            else
+                printf("error: %s\n", line.c_str());
         } else if (cmd == "plan") {
             std::string tn, layout;
             StreamCall c;

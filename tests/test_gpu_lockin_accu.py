@@ -27,7 +27,7 @@ ENTRY = "lockin_i32_accu_process"
 LANES = [1, 63, 64, 65, 1000]
 UPDATES = [1, 3, 33]
 KS = [0, 1, 3, 10]
-SPLIT_MAX = 40960  # kSplitMaxLanes (idsp_amd/csrc/dds_dev.h): the I and Q arms on two threads up to here
+SPLIT_MAX = 40960  # thr::kSplitMaxLanes (idsp_amd/csrc/dispatch_thresholds.h): the I and Q arms on two threads up to here
 
 
 def _ptr(t):
