@@ -65,10 +65,13 @@ class GpuBackend:
     the state and `y`) with what was uploaded."""
     name = "hip"
 
-    def __init__(self):
+    def __init__(self, on_stream=None):
+        """on_stream: True / False, or None for what IDSP_TEST_STREAM says"""
         import torch
 
         self.torch = torch
+        self.on_stream = on_stream
+        self.last_call = None  # the tests/_on_stream.py Call of the most recent call, when it ran under the arrangement
         self.e = H.engine()
         self.dev = torch.device("cuda:0")
         self.g = None  # the guarded buffers of the call in flight
@@ -102,11 +105,45 @@ class GpuBackend:
         self.torch.cuda.synchronize()
         self.g.check(op)
 
+    # IDSP_TEST_STREAM=1: every call below runs under the arrangement of tests/_on_stream.py -- decoys in the buffers, the true inputs
+    # copied in on a stream S behind a device-side delay, the call with stream = S, the results read back on S
+    # (tests/test_gpu_callers_stream.py replays the parity suites that way in a subprocess)
+    def _call(self, entry):
+        from tests import _on_stream as OS
+
+        if not (OS.enabled() if self.on_stream is None else self.on_stream):
+            return None
+        self._begin()
+        self.last_call = OS.Call(entry, self.g)
+        return self.last_call
+
+    def _stage(self, c, a, role, readonly=False):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        return c.stage(role, a, self._off(a.dtype.itemsize), readonly)
+
+    def _out(self, c, n, dtype, fill):
+        return c.out("y", n, dtype, fill, self._off(self.torch.empty(0, dtype=dtype).element_size()))
+
     def stream(self, op, cfg, n, state, x, lanes, frames, layout, inplace=False):
         import os
 
         torch = self.torch
         inplace = inplace or bool(os.environ.get("IDSP_TEST_INPLACE"))  # `Inplace::inplace` for every stream call
+        c = self._call(op)
+        if c is not None:
+            xs = self._stage(c, x, "x", readonly=not inplace)
+            ys = xs if inplace else self._out(c, xs.numel(), xs.dtype, -77 if xs.dtype == torch.int32 else float("nan")).reshape(xs.shape)
+            ss = self._stage(c, state, "state")
+            c.read(ys)
+            if ss is not None:
+                c.read(ss)
+            rc, got = c.run(lambda s: self.e.stream(op, cfg, n, ss, xs, ys, lanes, frames, layout, s))
+            self._end(op)
+            if ss is not None:
+                state[...] = got[1].view(np.uint32).reshape(state.shape)
+            return rc, got[0].view(x.dtype).reshape(np.shape(x))
         self._begin()
         xs = self._up(x, "x", readonly=not inplace)
         ys = xs if inplace else self._alloc(xs.numel(), xs.dtype).reshape(xs.shape)
@@ -124,6 +161,19 @@ class GpuBackend:
 
         torch = self.torch
         inplace = inplace or bool(os.environ.get("IDSP_TEST_INPLACE"))
+        c = self._call(op + "_bylane")
+        if c is not None:
+            xs, cs, ss = self._stage(c, x, "x", readonly=not inplace), self._stage(c, coef, "coef", readonly=True), self._stage(c, state, "state")
+            ys = xs if inplace else self._out(c, xs.numel(), xs.dtype, -77 if xs.dtype == torch.int32 else float("nan")).reshape(xs.shape)
+            c.read(ys)
+            if ss is not None:
+                c.read(ss)
+            head = (H._ptr(cs),) + (() if frac is None else (frac,)) + (n, H._ptr(ss), H._ptr(xs), H._ptr(ys), lanes, frames, layout)
+            rc, got = c.run(lambda s: self.e.fn[op + "_bylane"](*head, s))
+            self._end(op + "_bylane")  # the coefficient planes are read-only there
+            if ss is not None:
+                state[...] = got[1].view(np.uint32).reshape(state.shape)
+            return rc, got[0].view(x.dtype).reshape(np.shape(x))
         self._begin()
         xs, cs, ss = self._up(x, "x", readonly=not inplace), self._up(coef, "coef", readonly=True), self._up(state, "state")
         ys = xs if inplace else self._alloc(xs.numel(), xs.dtype).reshape(xs.shape)
@@ -139,9 +189,19 @@ class GpuBackend:
 
     def cfgcall(self, op, cfg, state, x, y_shape, y_dtype, lanes, frames, layout):
         torch = self.torch
+        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.int64): torch.int64}.get(np.dtype(y_dtype), torch.int32)
+        c = self._call(op)
+        if c is not None:
+            xs = self._stage(c, x, "x", readonly=True)
+            ys = self._out(c, int(np.prod(y_shape)), tdt, float("nan") if tdt == torch.float32 else -77)
+            ss = self._stage(c, state, "state")
+            c.read(ys), c.read(ss)
+            rc, got = c.run(lambda s: self.e.cfgcall(op, cfg, ss, xs, ys, lanes, frames, layout, s))
+            self._end(op)
+            state[...] = got[1].view(np.uint32).reshape(state.shape)
+            return rc, got[0].view(y_dtype).reshape(y_shape)
         self._begin()
         xs = self._up(x, "x", readonly=True)
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.int64): torch.int64}.get(np.dtype(y_dtype), torch.int32)
         ys = self._alloc(int(np.prod(y_shape)), tdt)
         ys.fill_(float("nan") if tdt == torch.float32 else -77)  # poison: every element must be written
         ss = self._up(state, "state")
@@ -152,6 +212,13 @@ class GpuBackend:
 
     def cossin(self, phases):
         torch = self.torch
+        c = self._call("cossin_i32")
+        if c is not None:
+            ps = self._stage(c, np.ascontiguousarray(phases, dtype=np.int32), "x", readonly=True)
+            out = c.read(self._out(c, ps.numel() * 2, torch.int32, -77))
+            rc, got = c.run(lambda s: self.e.fn["cossin_i32"](H._ptr(ps), H._ptr(out), ps.numel(), s))
+            self._end("cossin_i32")
+            return rc, got[0].view(np.int32).reshape(-1, 2)
         self._begin()
         ps = self._up(np.ascontiguousarray(phases, dtype=np.int32), "x", readonly=True)
         out = self._alloc(ps.numel() * 2, torch.int32)
@@ -161,6 +228,13 @@ class GpuBackend:
 
     def atan2(self, xy):
         torch = self.torch
+        c = self._call("atan2_i32")
+        if c is not None:
+            xs = self._stage(c, np.ascontiguousarray(xy, dtype=np.int32), "x", readonly=True)
+            out = c.read(self._out(c, xs.numel() // 2, torch.int32, -77))
+            rc, got = c.run(lambda s: self.e.fn["atan2_i32"](H._ptr(xs), H._ptr(out), out.numel(), s))
+            self._end("atan2_i32")
+            return rc, got[0].view(np.int32)
         self._begin()
         xs = self._up(np.ascontiguousarray(xy, dtype=np.int32), "x", readonly=True)
         out = self._alloc(xs.numel() // 2, torch.int32)
@@ -170,6 +244,15 @@ class GpuBackend:
 
     def dds(self, state, lanes, frames, layout):
         torch = self.torch
+        c = self._call("dds_i32")
+        if c is not None:
+            ss = self._stage(c, state, "state")
+            out = c.read(self._out(c, lanes * frames * 2, torch.int32, -77))
+            c.read(ss)
+            rc, got = c.run(lambda s: self.e.fn["dds_i32"](H._ptr(ss), H._ptr(out), lanes, frames, layout, s))
+            self._end("dds_i32")
+            state[...] = got[1].view(np.uint32).reshape(state.shape)
+            return rc, got[0].view(np.int32)
         self._begin()
         ss = self._up(state, "state")
         out = self._alloc(lanes * frames * 2, torch.int32)

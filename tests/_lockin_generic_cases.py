@@ -39,14 +39,14 @@ def sections_f32(n, rng, f0=None):
     return arr, rows
 
 
-def call_lo(lib, name, cfg, n, state, x, lo, y, lanes, frames, layout, with_stream):
+def call_lo(lib, name, cfg, n, state, x, lo, y, lanes, frames, layout, with_stream, stream=None):
     """The `_lo` entries: (cfg[, n], state, x, lo, y, lanes, frames, layout[, stream])."""
     args = [C.cast(cfg, C.c_void_p) if n is not None else C.byref(cfg)]
     if n is not None:
         args.append(n)
     args += [H._ptr(state), H._ptr(x), H._ptr(lo), H._ptr(y), lanes, frames, layout]
     if with_stream:
-        args.append(None)
+        args.append(stream)
     return lib.fn[name](*args)
 
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import _harness as H
+from tests import _on_stream as OS
 from tests import test_gpu_frame_major_staged as FMS
 from tests.test_gpu_pitch import DEV, SENT, init_state, p, sample, tdtype
 
@@ -71,6 +72,16 @@ def test_cascades_of_five_to_eight_sections(gpu, op, dt, mk):
             st0 = init_state(rng, dt, words, lanes)
             so = st0.copy()
             assert o.stream(op, cfg, n, so, xh, want, lanes, frames, FM) == 0
+            if OS.enabled():  # IDSP_TEST_STREAM=1: the same call and the same assertions under the arrangement of tests/_on_stream.py
+                full, decoy = (np.full((frames, pitch), SENT, dtype=xh.dtype) for _ in range(2))
+                full[:, off:off + lanes], decoy[:, off:off + lanes] = xh, 0
+                rc, yh, sh, _ = OS.pitch_call(gpu, op + "_pitch", cfg, n, st0, full, decoy, off, pitch, pitch, frames * pitch, lanes, frames, FM, inplace, SENT)
+                assert rc == 0 and kernel_of(gpu).startswith("stream_frame_major_duo<"), (gpu.err(), kernel_of(gpu))
+                yv = yh.reshape(frames, pitch)
+                assert np.array_equal(yv[:, off:off + lanes].view(np.uint32), want.view(np.uint32)), (op, n, lanes)
+                assert np.array_equal(sh, so), (op, n, "state")
+                assert (yv[:, :off] == SENT).all() and (yv[:, off + lanes:] == SENT).all()
+                continue
             xb = torch.full((frames * pitch,), SENT, dtype=tdtype(dt), device=DEV)
             xb.view(frames, pitch)[:, off:off + lanes] = torch.from_numpy(xh).to(DEV)
             yb = xb if inplace else torch.full((frames * pitch,), SENT, dtype=tdtype(dt), device=DEV)

@@ -16,10 +16,15 @@ FM, LM = H.FM, H.LM
 DEV = "cuda:0"
 
 
+def state_f64(rng, words, lanes):
+    """[words, lanes] uint32: finite f64 values as (lo, hi) word planes"""
+    return rng.standard_normal((words // 2, lanes)).view(np.uint32).reshape(words // 2, lanes, 2).transpose(0, 2, 1).reshape(words, lanes).copy()
+
+
 def pair(name, cfg, words, nin_of, nout_of, shapes, layout, rng):
     o, e = H.oracle(), H.engine()
     for lanes, frames in shapes:
-        st0 = rng.standard_normal((words // 2, lanes)).view(np.uint32).reshape(words // 2, lanes, 2).transpose(0, 2, 1).reshape(words, lanes).copy()
+        st0 = state_f64(rng, words, lanes)
         g = Guards(DEV)  # every buffer between guard bands, x read-only (tests/_guard.py)
         so, sg = st0.copy(), g.upload("state", st0)
         for rep in range(2):

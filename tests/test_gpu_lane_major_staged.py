@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests import _harness as H
+from tests import _on_stream as OS
 from tests._guard import Guards
 from tests.test_gpu_pitch import DEV, SENT, cases, init_state, p, sample, tdtype
 
@@ -42,6 +43,16 @@ def run_case(eng, op, cfg, n, words, dt, rng, lanes, frames, pitch, inplace):
     so = st0.copy()
     assert o.stream(op, cfg, n, so, xh, want, lanes, frames, LM) == 0
     t = tdtype(dt)
+    if OS.enabled():  # IDSP_TEST_STREAM=1: the same call and the same assertions under the arrangement of tests/_on_stream.py
+        full, decoy = (np.full((lanes, pitch), SENT, dtype=xh.dtype) for _ in range(2))
+        full[:, :frames], decoy[:, :frames] = xh, 0
+        rc, yh, sh, _ = OS.pitch_call(eng, op + "_pitch", cfg, n, st0, full, decoy, 0, pitch, pitch, lanes * pitch, lanes, frames, LM, inplace, SENT)
+        assert rc == 0, (op, eng.err())
+        yv = yh.reshape(lanes, pitch)
+        assert np.array_equal(yv[:, :frames].view(np.uint8), want.view(np.uint8)), (op, lanes, frames, pitch, inplace)
+        assert np.array_equal(sh, so), (op, lanes, frames, "state")
+        assert (yv[:, frames:] == SENT).all(), (op, "row padding must stay untouched")
+        return
     g = Guards(DEV)  # guard bands around x, y and the state; a non-in-place x (padding included) is read-only (tests/_guard.py)
     xb = g.full("x", lanes * pitch, t, SENT)
     xb.view(lanes, pitch)[:, :frames] = torch.from_numpy(xh).to(DEV)
