@@ -3,6 +3,6 @@
 
 namespace idsp {
 namespace cic {
-template int run_orders<int32_t, true, 4>(const idsp_cic *, void *, const int32_t *, int32_t *, size_t, size_t, int, void *);
+template int run_orders<int32_t, true, 4>(const CicPlan &, const idsp_cic *, uint32_t *, const int32_t *, int32_t *, size_t, size_t, int, hipStream_t);
 }  // namespace cic
 }  // namespace idsp

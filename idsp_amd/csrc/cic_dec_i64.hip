@@ -4,7 +4,7 @@
 
 namespace idsp {
 namespace cic {
-extern template int run_orders<int64_t, true, 4>(const idsp_cic *, void *, const int64_t *, int64_t *, size_t, size_t, int, void *);
+extern template int run_orders<int64_t, true, 4>(const CicPlan &, const idsp_cic *, uint32_t *, const int64_t *, int64_t *, size_t, size_t, int, hipStream_t);
 }  // namespace cic
 }  // namespace idsp
 

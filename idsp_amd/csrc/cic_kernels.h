@@ -460,12 +460,6 @@ __global__ __launch_bounds__(kBlock) void cic_int_lm_kernel(const idsp_cic cfg, 
     c.store(st, lanes, lane, m);
 }
 
-inline bool cic_no_lm_tiles()
-{
-    static const bool v = diag_env("IDSP_CIC_NO_LM_TILES") != nullptr;
-    return v;
-}
-
 inline int cfg_check(const idsp_cic *c)
 {
     if (!c) return fail(IDSP_EINVAL, "cfg is NULL");
@@ -475,86 +469,73 @@ inline int cfg_check(const idsp_cic *c)
     return IDSP_OK;
 }
 
-// Orders NLO .. NLO+2; the two halves (NLO = 1, 4) are instantiated in separate translation units.
+// The lane-per-thread kernels (CicForm::LaneTiles, CicForm::Lane) of orders NLO .. NLO+2; the two halves (NLO = 1, 4) are instantiated in
+// separate translation units.
 template <class T, bool DEC, int NLO>
-int run_orders(const idsp_cic *cfg, void *state, const T *x, T *y, size_t lanes, size_t frames, int layout, void *stream)
+int run_orders(const CicPlan &p, const idsp_cic *cfg, uint32_t *st, const T *x, T *y, size_t lanes, size_t frames, int layout, hipStream_t s)
+{
+    static_assert(kBlock == thr::kCicBlockLanes && kTileVecs == thr::kCicTileVecs, "plan_cic counts these blocks and tiles");
+    const dim3 grid(p.grid), block(kBlock);
+    note_kernel(cic_plan_name(p));
+    const auto launch = [&](auto n, auto v) {
+        constexpr int N = NLO + decltype(n)::value, VPC = decltype(v)::value;
+        if constexpr (VPC > 0) {
+            if (p.form == CicForm::LaneTiles) {
+                if constexpr (DEC)
+                    hipLaunchKernelGGL((cic_dec_lm_kernel<T, N, VPC>), grid, block, 0, s, *cfg, st, x, y, lanes, frames);
+                else
+                    hipLaunchKernelGGL((cic_int_lm_kernel<T, N, VPC>), grid, block, 0, s, *cfg, st, x, y, lanes, frames);
+                return;
+            }
+        }
+        if constexpr (DEC)
+            hipLaunchKernelGGL((cic_dec_kernel<T, N, VPC>), grid, block, 0, s, *cfg, st, x, y, lanes, frames, layout);
+        else
+            hipLaunchKernelGGL((cic_int_kernel<T, N, VPC>), grid, block, 0, s, *cfg, st, x, y, lanes, frames, layout);
+    };
+    const auto by_width = [&](auto n) {
+        switch (p.vpc) {
+            case 1: return launch(n, int_c<1>{});
+            case 2: return launch(n, int_c<2>{});
+            case 4: return launch(n, int_c<4>{});
+            case 8: return launch(n, int_c<8>{});
+            case 16: return launch(n, int_c<16>{});
+            default: return launch(n, int_c<0>{});
+        }
+    };
+    switch (cfg->order - NLO) {
+        case 0: by_width(int_c<0>{}); break;
+        case 1: by_width(int_c<1>{}); break;
+        case 2: by_width(int_c<2>{}); break;
+    }
+    return launch_status();
+}
+
+// The entry: arguments, plan_cic (resample_plan.h), the launcher of the plan's form.
+template <class T, bool DEC>
+int run(const idsp_cic *cfg, void *state, const T *x, T *y, size_t lanes, size_t frames, int layout, void *stream)
 {
     int rc = cfg_check(cfg);
     if (rc) return rc;
     if ((rc = check_stream_args(cfg, 1, state, x, y, lanes, frames, layout))) return rc;
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    const dim3 grid(unsigned((lanes + kBlock - 1) / kBlock)), block(kBlock);
+    static const CicSwitches sw = read_cic_switches(diag_env);  // once per process
+    CicCall c;
+    c.dec = DEC, c.elem_bytes = int(sizeof(T)), c.order = cfg->order, c.rate = cfg->rate;
+    c.lanes = lanes, c.frames = frames, c.layout = layout;
+    c.x = reinterpret_cast<uintptr_t>(x), c.y = reinterpret_cast<uintptr_t>(y);
+    const CicPlan p = plan_cic(c, sw);
     uint32_t *st = static_cast<uint32_t *>(state);
     hipStream_t s = as_stream(stream);
-    // whole 16-byte pieces per chunk and at least 64 chunks: one wave per lane (cic_ring.h; the decimator in LANE_MAJOR only)
-    if (layout == IDSP_LANE_MAJOR || !DEC) {
-        int rr;
+    if (p.form == CicForm::RingLm || p.form == CicForm::RingFm) {
         if constexpr (DEC)
-            rr = cic_ring_dec(cfg, st, x, y, lanes, frames, s);
+            return cic_ring_dec_launch(p, cfg, st, x, y, lanes, frames, s);
         else
-            rr = cic_ring_int(cfg, st, x, y, lanes, frames, layout == IDSP_LANE_MAJOR, s);
-        if (rr == 0) return launch_status();
-        if (rr == 2) return IDSP_EHIP;
+            return cic_ring_int_launch(p, cfg, st, x, y, lanes, frames, s);
     }
-    // vectors per chunk when the chunk is a whole number of 16-byte vectors and the rows are aligned
-    using V = Vec16<T>;
-    const size_t R = size_t(cfg->rate) + 1;
-    int vpc = 0;
-    if (R % V::n == 0 && reinterpret_cast<uintptr_t>(DEC ? static_cast<const void *>(x) : static_cast<const void *>(y)) % 16 == 0) {
-        const size_t v = R / V::n;
-        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) vpc = int(v);
-    }
-    // LANE_MAJOR tile kernels: whole waves, at least one whole tile
-    const bool lm_tiles = layout == IDSP_LANE_MAJOR && vpc > 0 && lanes % kBlock == 0 && frames >= size_t(kTileVecs / (vpc ? vpc : 1)) &&
-                          reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
-                          (frames * R * sizeof(T)) % 16 == 0 && !cic_no_lm_tiles();
-#define IDSP_CIC_LAUNCH(NN, VV)                                                                                       \
-    do {                                                                                                              \
-        note_kernel(DEC ? "cic_dec_kernel" : "cic_int_kernel");                                                                                                              \
-        if constexpr (VV > 0) {                                                                                       \
-            if (lm_tiles) {                                                                                           \
-                if constexpr (DEC)                                                                                    \
-                    hipLaunchKernelGGL((cic_dec_lm_kernel<T, NN, VV>), grid, block, 0, s, *cfg, st, x, y, lanes, frames); \
-                else                                                                                                  \
-                    hipLaunchKernelGGL((cic_int_lm_kernel<T, NN, VV>), grid, block, 0, s, *cfg, st, x, y, lanes, frames); \
-                break;                                                                                                \
-            }                                                                                                         \
-        }                                                                                                             \
-        if constexpr (DEC)                                                                                            \
-            hipLaunchKernelGGL((cic_dec_kernel<T, NN, VV>), grid, block, 0, s, *cfg, st, x, y, lanes, frames, layout); \
-        else                                                                                                          \
-            hipLaunchKernelGGL((cic_int_kernel<T, NN, VV>), grid, block, 0, s, *cfg, st, x, y, lanes, frames, layout); \
-    } while (0)
-#define IDSP_CIC_CASE(NN)                            \
-    case NN:                                         \
-        switch (vpc) {                               \
-            case 1: IDSP_CIC_LAUNCH(NN, 1); break;   \
-            case 2: IDSP_CIC_LAUNCH(NN, 2); break;   \
-            case 4: IDSP_CIC_LAUNCH(NN, 4); break;   \
-            case 8: IDSP_CIC_LAUNCH(NN, 8); break;   \
-            case 16: IDSP_CIC_LAUNCH(NN, 16); break; \
-            default: IDSP_CIC_LAUNCH(NN, 0); break;  \
-        }                                            \
-        break;
-    switch (cfg->order) {
-        IDSP_CIC_CASE(NLO)
-        IDSP_CIC_CASE(NLO + 1)
-        IDSP_CIC_CASE(NLO + 2)
-    }
-#undef IDSP_CIC_CASE
-#undef IDSP_CIC_LAUNCH
-    return launch_status();
+    return cfg->order <= 3 ? run_orders<T, DEC, 1>(p, cfg, st, x, y, lanes, frames, layout, s)
+                           : run_orders<T, DEC, 4>(p, cfg, st, x, y, lanes, frames, layout, s);
 }
-
-template <class T, bool DEC>
-int run(const idsp_cic *cfg, void *state, const T *x, T *y, size_t lanes, size_t frames, int layout, void *stream)
-{
-    const int rc = cfg_check(cfg);
-    if (rc) return rc;
-    return cfg->order <= 3 ? run_orders<T, DEC, 1>(cfg, state, x, y, lanes, frames, layout, stream)
-                           : run_orders<T, DEC, 4>(cfg, state, x, y, lanes, frames, layout, stream);
-}
-
 
 }  // namespace cic
 }  // namespace idsp

@@ -32,6 +32,7 @@
 #include "common.h"
 #include "idsp_hip.h"
 #include "lds_dma.h"
+#include "resample_plan.h"
 
 namespace idsp {
 namespace cicr {
@@ -575,12 +576,10 @@ __global__ __launch_bounds__(kFmLanes *kW) void cic_int_ring_fm(const IntCoef<T,
 
 }  // namespace cicr
 
-// 0: a ring kernel was launched; 1: shape not covered (the caller falls back to cic_kernels.h); 2: HIP error
-int cic_ring_dec(const idsp_cic *cfg, uint32_t *st, const int32_t *x, int32_t *y, size_t lanes, size_t frames, hipStream_t stream);
-int cic_ring_dec(const idsp_cic *cfg, uint32_t *st, const int64_t *x, int64_t *y, size_t lanes, size_t frames, hipStream_t stream);
-int cic_ring_int(const idsp_cic *cfg, uint32_t *st, const int32_t *x, int32_t *y, size_t lanes, size_t frames, bool lane_major,
-                 hipStream_t stream);
-int cic_ring_int(const idsp_cic *cfg, uint32_t *st, const int64_t *x, int64_t *y, size_t lanes, size_t frames, bool lane_major,
-                 hipStream_t stream);
+// cic_ring_dec.hip / cic_ring_int.hip (T = int32_t, int64_t): launch the ring kernel of the plan (CicForm::RingLm, for the interpolator also RingFm)
+template <class T>
+int cic_ring_dec_launch(const CicPlan &p, const idsp_cic *cfg, uint32_t *st, const T *x, T *y, size_t lanes, size_t frames, hipStream_t stream);
+template <class T>
+int cic_ring_int_launch(const CicPlan &p, const idsp_cic *cfg, uint32_t *st, const T *x, T *y, size_t lanes, size_t frames, hipStream_t stream);
 
 }  // namespace idsp

@@ -31,12 +31,6 @@ inline Poly power(uint64_t e, int n)
     return r;
 }
 
-inline bool no_ring()
-{
-    static const bool v = diag_env("IDSP_CIC_NO_RING") != nullptr;
-    return v;
-}
-
 // scan coefficients g_d(R 2^k), k = 0 .. 5
 template <class T, int N>
 inline cicr::ScanCoef<T, N> scan_coef(size_t R)
@@ -50,18 +44,31 @@ inline cicr::ScanCoef<T, N> scan_coef(size_t R)
     return coef;
 }
 
-// whole 16-byte pieces per chunk (1, 2, 4 or 8 of them), at least one whole block of 64 chunks (below that the
-// lane-per-thread kernels have as much parallelism and less to set up), lanes within the grid limit; `hi` = the
-// high-rate tensor.  Returns the pieces per chunk, or 0.
-template <class T>
-inline int ring_pieces(const idsp_cic *cfg, const void *hi, size_t lanes, size_t frames)
+// f(N, PPT) with the order (1..6) and the pieces per chunk (1, 2, 4, 8: CicPlan::ppt) as compile-time constants: both ring launchers' ladder
+template <class F>
+inline int for_order_pieces(int order, int ppt, F &&f)
 {
-    const size_t fb = (size_t(cfg->rate) + 1) * sizeof(T);
-    if (no_ring() || fb % 16 != 0 || fb > 128 || (fb & (fb - 1)) != 0 || frames < size_t(cicr::kW) || reinterpret_cast<uintptr_t>(hi) % 16 != 0 ||
-        lanes > 0x7fffffffu)
-        return 0;
-    return int(fb / 16);
+    const auto pieces = [&](auto n) {
+        switch (ppt) {
+            case 1: return f(n, int_c<1>{});
+            case 2: return f(n, int_c<2>{});
+            case 4: return f(n, int_c<4>{});
+            case 8: return f(n, int_c<8>{});
+            default: return fail(IDSP_EINVAL, "no Cic ring kernel for %d pieces per chunk", ppt);
+        }
+    };
+    switch (order) {
+        case 1: return pieces(int_c<1>{});
+        case 2: return pieces(int_c<2>{});
+        case 3: return pieces(int_c<3>{});
+        case 4: return pieces(int_c<4>{});
+        case 5: return pieces(int_c<5>{});
+        case 6: return pieces(int_c<6>{});
+        default: return fail(IDSP_EINVAL, "Cic order N = %d not in 1..%d", order, IDSP_CIC_MAX_ORDER);
+    }
 }
+
+static_assert(cicr::kW == thr::kCicRingMinFrames && cicr::kFmLanes == thr::kCicRingFmLanes, "plan_cic: one whole block of chunks, groups of 16 lanes");
 
 }  // namespace cicr_host
 }  // namespace idsp

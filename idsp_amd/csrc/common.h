@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "idsp_hip.h"
 
@@ -113,6 +114,10 @@ void note_kernel(const char *kernel, const char *detail = nullptr);
 void note_kernel_also(const char *also);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// a run-time value as a compile-time constant: what the `for_*` ladders (dds_dev.h, hbf_taps.h, cic_ring_host.h) pass to their functor
+template <int V>
+using int_c = std::integral_constant<int, V>;
 
 // Checks shared by every lane-streaming entry point (the reference's
 // debug_assert / const-assert preconditions, reported instead of aborting).

@@ -40,8 +40,6 @@ inline LockinPlan lockin_plan_for(LockinArms arms, LockinLo lo, int readout, int
 }
 
 // f(N, K) / f(NS) with the configuration as compile-time constants: `[Lowpass<N>; K]`, 1..4 biquad sections (callers have checked n)
-template <int V>
-using int_c = std::integral_constant<int, V>;
 template <class F>
 inline int for_nk(const idsp_lockin_i32 *cfg, F &&f)
 {

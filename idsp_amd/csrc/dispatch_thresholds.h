@@ -3,10 +3,12 @@
 // comes from is named, profiles/NOTES.md has the numbers, and tests/test_gpu_dispatch_table.py pins the kernel taken at every BASELINE
 // shape and on both sides of every cliff listed here; tests/test_stream_plan.py pins the same table and both sides of every threshold without
 // a GPU, through `plan_stream` (stream_plan.h), which is the one reader of what follows — but for the lock-in section, whose one reader is
-// `plan_lockin` (lockin_plan.h; tests/test_lockin_plan.py pins both sides of each of its names the same way).
+// `plan_lockin` (lockin_plan.h; tests/test_lockin_plan.py pins both sides of each of its names the same way), and for the half-band and Cic
+// sections, read by `plan_hbf` / `plan_cic` (resample_plan.h; tests/test_resample_plan.py).
 #pragma once
 
 #include <cstddef>
+#include <cstdint>
 
 namespace idsp {
 namespace thr {
@@ -67,6 +69,33 @@ constexpr size_t kLmStagedMinRowBytes = 128;
 constexpr unsigned kStaggerMinWorkgroups = 512;                     // launches of at least two workgroups per CU
 constexpr size_t kStaggerMinFrames = 2048, kStaggerMaxFrames = 8192;  // long enough to pay, short enough not to drift apart anyway
 constexpr unsigned kLockinStaggerTicks = 600, kFmDiscStaggerTicks = 1200;  // 10 ns ticks between the four CU groups of an XCD
+
+// ---- half-band (plan_hbf, resample_plan.h; tests/test_resample_plan.py pins both sides of each name of this section and the next) ----
+// Kernel geometry, not measured cliffs: what the kernels of the two resampling families are built for.  (Fixed-width types: the constants of the
+// other sections, `size_t` / `int` / `unsigned`, are what tests/_stream_proc_cases.py collects as the stream launcher's thresholds.)
+// the vector kernels of both resampling families move whole 16-byte pieces: the wide buffer (x of a decimator, y of an interpolator)
+// starts on this grid, and so does every LaneMajor row of it
+constexpr uint64_t kPieceBytes = 16;
+// kernels of one workgroup per lane (or per lane group) keep the lane count inside a 31-bit grid; the lane-per-thread kernels take the rest
+constexpr uint64_t kGridMaxLanes = 0x7fffffff;
+// FrameMajor: a frame of at least one piece, 2^stages floats — from this many stages; one stage stays on the generic kernel
+constexpr int32_t kHbfFmMinStages = 2;
+// the LDS-DMA ring decimator (hbf_ring.h) exists for /16 only, on whole groups of this many lanes
+constexpr int32_t kHbfRingStages = 4;
+constexpr uint64_t kHbfRingLanes = 16;
+// hbf_dec_block_fm / hbf_int_block_fm (hbf_wave.h): whole workgroups of this many lanes, else the wave-per-lane kernel
+constexpr uint64_t kHbfBlockLanes = 4;
+
+// ---- Cic (plan_cic, resample_plan.h) ---------------------------------------------------------------------------------------------------
+// wave-per-lane ring kernels (cic_ring.h): a chunk of rate + 1 samples is 1, 2, 4 or 8 whole pieces, at least one whole block of 64 chunks
+// (below that the lane-per-thread kernels have as much parallelism and less to set up); FrameMajor (interpolator) on whole groups of 16 lanes
+constexpr uint64_t kCicRingMinChunkBytes = 16, kCicRingMaxChunkBytes = 128;
+constexpr uint64_t kCicRingMinFrames = 64;
+constexpr uint64_t kCicRingFmLanes = 16;
+// lane-per-thread kernels (cic_kernels.h): blocks of 64 lanes; chunks of 1, 2, 4, 8 or 16 whole vectors are moved as vectors, and the
+// LaneMajor tile form moves 64 lanes x 16 vectors through LDS: whole blocks, at least one whole tile
+constexpr uint64_t kCicBlockLanes = 64;
+constexpr uint64_t kCicTileVecs = 16;
 
 // ---- lock-in (plan_lockin, lockin_plan.h; the measurements are quoted where each is read) ------------------------------------------
 // largest lane count that still runs the I and Q arms on two threads of the stream kernels (IDSP_SPLIT_MAX_LANES overrides); the multi-wave

@@ -28,21 +28,16 @@
 
 #include "common.h"
 #include "hbf_taps.h"
+#include "resample_plan.h"
 
 namespace idsp {
 
 bool hbf_cfg_ok(const idsp_hbf_cascade_f32 *c);  // api_util.hip
-// hbf_wave_{dec,int}.hip: statically specialised kernels for the built-in cascades (0 = launched)
-int hbf_wave_dec(int tap_set, int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames,
-                 bool lane_major, hipStream_t stream);
-int hbf_wave_int(int tap_set, int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames,
-                 bool lane_major, hipStream_t stream);
-// hbf_ring_dec.hip: LDS-DMA ring decimators (0 = launched, 1 = shape not covered, 2 = HIP error)
-// hbf_blk_dec.hip: register-blocked decimators (same return codes)
-int hbf_blk_dec(int tap_set, int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames,
-                bool lane_major, hipStream_t stream);
-int hbf_ring_dec(int tap_set, int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames,
-                 bool lane_major, hipStream_t stream);
+// one launcher per family of specialised kernels, each in the .hip of its name: what the plan says, an idsp status back
+int hbf_blk_launch(const HbfCall &c, const HbfPlan &p, uint32_t *st, const float *x, float *y, hipStream_t stream);
+int hbf_ring_launch(const HbfCall &c, const HbfPlan &p, uint32_t *st, const float *x, float *y, hipStream_t stream);
+int hbf_wave_dec_launch(const HbfCall &c, const HbfPlan &p, uint32_t *st, const float *x, float *y, hipStream_t stream);
+int hbf_wave_int_launch(const HbfCall &c, const HbfPlan &p, uint32_t *st, const float *x, float *y, hipStream_t stream);
 
 namespace {
 
@@ -559,52 +554,35 @@ int builtin_tap_set(const idsp_hbf_cascade_f32 *cfg, bool dec)
     return -1;
 }
 
-template <class K>
-int launch_hbf(K kernel, const idsp_hbf_cascade_f32 *cfg, bool dec, void *state, const float *x, float *y, size_t lanes,
-               size_t frames, int layout, void *stream)
+int launch_hbf(const idsp_hbf_cascade_f32 *cfg, bool dec, void *state, const float *x, float *y, size_t lanes, size_t frames, int layout, void *stream)
 {
     if (!hbf_cfg_ok(cfg)) return fail(IDSP_EINVAL, "invalid hbf cascade (stages 1..5, taps 1..32 per stage)");
     if (layout != IDSP_FRAME_MAJOR && layout != IDSP_LANE_MAJOR) return fail(IDSP_EINVAL, "bad layout %d", layout);
     if (lanes && (!state || (frames && (!x || !y)))) return fail(IDSP_EINVAL, "state, x or y is NULL");
     if (lanes > (size_t(1) << 31) - 1 || frames > (size_t(1) << 40)) return fail(IDSP_EINVAL, "lanes/frames out of range");
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    // f32 slices are 4-byte aligned in the reference; the generic kernels' 8- and 16-byte global accesses are legal at that
-    // alignment on gfx950 (unaligned access mode), the wave kernels below are taken only when their accesses are aligned
-    // Fast path: the reference's own cascades run on the specialised one-wave-per-lane
-    // kernels when every 16-byte access they make is aligned; anything else (custom taps,
-    // odd shapes) takes the generic workgroup-per-lane kernel below.
-    static const bool force_generic = diag_env("IDSP_HBF_GENERIC") != nullptr;
-    const int ts = force_generic ? -1 : builtin_tap_set(cfg, dec);
-    const bool lm = layout == IDSP_LANE_MAJOR;
-    const size_t R = size_t(1) << cfg->stages;
-    const void *wide = dec ? static_cast<const void *>(x) : static_cast<const void *>(y);
-    if (ts >= 0 && reinterpret_cast<uintptr_t>(wide) % 16 == 0 && (lm ? (frames * R) % 4 == 0 : R >= 4)) {
-        // decimators: the LDS-DMA ring kernels of hbf_ring.h first (LANE_MAJOR any cascade; FRAME_MAJOR /16 on whole
-        // 16-lane groups), then the wave-per-lane kernels of hbf_wave.h
-        static const bool no_ring = diag_env("IDSP_HBF_NO_RING") != nullptr, no_blk = diag_env("IDSP_HBF_NO_BLK") != nullptr;
-        if (dec && !no_blk) {
-            const int rb = hbf_blk_dec(ts, cfg->stages, static_cast<uint32_t *>(state), x, y, lanes, frames, lm, as_stream(stream));
-            if (rb == 0) return launch_status();
-            if (rb != 1) return IDSP_EHIP;
-        }
-        if (dec && !no_ring) {
-            const int rr = hbf_ring_dec(ts, cfg->stages, static_cast<uint32_t *>(state), x, y, lanes, frames, lm, as_stream(stream));
-            if (rr == 0) return launch_status();
-            if (rr != 1) return IDSP_EHIP;
-        }
-        const int rc = dec ? hbf_wave_dec(ts, cfg->stages, static_cast<uint32_t *>(state), x, y, lanes, frames, lm, as_stream(stream))
-                           : hbf_wave_int(ts, cfg->stages, static_cast<uint32_t *>(state), x, y, lanes, frames, lm, as_stream(stream));
-        if (rc == 0) return launch_status();
+    static const HbfSwitches sw = read_hbf_switches(diag_env);  // once per process
+    HbfCall c;
+    c.dec = dec, c.tap_set = builtin_tap_set(cfg, dec), c.stages = cfg->stages;
+    c.lanes = lanes, c.frames = frames, c.layout = layout;
+    c.wide = reinterpret_cast<uintptr_t>(dec ? static_cast<const void *>(x) : static_cast<const void *>(y));
+    const HbfPlan p = plan_hbf(c, sw);
+    uint32_t *st = static_cast<uint32_t *>(state);
+    switch (p.form) {
+        case HbfForm::Generic: break;
+        case HbfForm::BlkLm: return hbf_blk_launch(c, p, st, x, y, as_stream(stream));
+        case HbfForm::RingFm: return hbf_ring_launch(c, p, st, x, y, as_stream(stream));
+        default: return dec ? hbf_wave_dec_launch(c, p, st, x, y, as_stream(stream)) : hbf_wave_int_launch(c, p, st, x, y, as_stream(stream));
     }
     HbfArgs a;
     int lds_words = 0;
     fill_args(cfg, dec, a, lds_words);
     const size_t bytes = size_t(lds_words) * sizeof(float);
+    const auto kernel = dec ? hbf_dec_kernel : hbf_int_kernel;
     if (bytes > 64 * 1024)
         IDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
-    note_kernel(dec ? "hbf_dec_kernel (generic taps)" : "hbf_int_kernel (generic taps)");
-    hipLaunchKernelGGL(kernel, dim3(unsigned(layout == IDSP_LANE_MAJOR ? lanes : 8 * ((lanes + 7) / 8))), dim3(kThreads), bytes, as_stream(stream), a,
-                       static_cast<uint32_t *>(state), x, y, lanes, frames, layout == IDSP_LANE_MAJOR ? 1 : 0);
+    note_kernel(hbf_plan_name(p));
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(kThreads), bytes, as_stream(stream), a, st, x, y, lanes, frames, layout == IDSP_LANE_MAJOR ? 1 : 0);
     return launch_status();
 }
 
@@ -618,13 +596,13 @@ extern "C" {
 int idsp_hbf_dec_f32(const idsp_hbf_cascade_f32 *cfg, void *state, const float *x, float *y, size_t lanes,
                      size_t frames, int layout, void *stream)
 {
-    return launch_hbf(hbf_dec_kernel, cfg, true, state, x, y, lanes, frames, layout, stream);
+    return launch_hbf(cfg, true, state, x, y, lanes, frames, layout, stream);
 }
 
 int idsp_hbf_int_f32(const idsp_hbf_cascade_f32 *cfg, void *state, const float *x, float *y, size_t lanes,
                      size_t frames, int layout, void *stream)
 {
-    return launch_hbf(hbf_int_kernel, cfg, false, state, x, y, lanes, frames, layout, stream);
+    return launch_hbf(cfg, false, state, x, y, lanes, frames, layout, stream);
 }
 
 size_t idsp_fir_sym_state_words(const idsp_fir_sym_f32 *cfg)

@@ -443,13 +443,8 @@ __global__ __launch_bounds__(kW) void hbf_dec_blk_lm(uint32_t *st, const float *
 #define IDSP_HBF_BLK_PM kPmAll
 #endif
 template <int TS, int S>
-int launch_blk(uint32_t *st, const float *x, float *y, size_t lanes, size_t frames, bool lm, hipStream_t stream)
+int launch_blk(const HbfPlan &p, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames, hipStream_t stream)
 {
-    if (!lm) return 1;                  // FrameMajor: hbf_ring.h
-    if (lanes > 0x7fffffffu) return 1;  // one workgroup per lane in a 31-bit grid: not covered beyond, as in cic_ring_host.h
-#ifdef IDSP_HBF_BLK_OFF  // A/B harness (tools/exp_hbf_ab.py): the wave kernels of hbf_wave.h instead
-    return 1;
-#endif
     using L = BLay<TS, S, IDSP_HBF_BLK_PM>;
     // (IDSP_DIAG=1 IDSP_HBF_LDS_PAD=n: n more bytes of LDS per wave — fewer waves per CU, to read the occupancy slope)
     static const size_t pad = [] {
@@ -457,17 +452,11 @@ int launch_blk(uint32_t *st, const float *x, float *y, size_t lanes, size_t fram
         return e ? size_t(strtoul(e, nullptr, 10)) & ~size_t(15) : size_t(0);
     }();
     const size_t bytes = (size_t(4 * L::M(0)) + kSC + up4(L::words)) * sizeof(float) + pad;
-    if (ensure_dyn_lds<&hbf_dec_blk_lm<L>>(bytes)) return 2;
-    note_kernel("hbf_dec_blk[LaneMajor]", typeid(L).name());
-    hipLaunchKernelGGL((hbf_dec_blk_lm<L>), dim3(unsigned(lanes)), dim3(kW), bytes, stream, st, x, y, lanes, frames);
-    return 0;
+    if (const int rc = ensure_dyn_lds<&hbf_dec_blk_lm<L>>(bytes)) return rc;
+    note_kernel(hbf_plan_name(p), typeid(L).name());
+    hipLaunchKernelGGL((hbf_dec_blk_lm<L>), dim3(p.grid), dim3(kW), bytes, stream, st, x, y, lanes, frames);
+    return launch_status();
 }
 
 }  // namespace hbfb
-
-// Returns 0 when the blocked kernel was launched, 1 when the request is not covered (the caller goes on to hbf_ring.h /
-// hbf_wave.h), 2 on a HIP error (idsp_last_error() holds the text).
-int hbf_blk_dec(int tap_set, int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames,
-                bool lane_major, hipStream_t stream);
-
 }  // namespace idsp

@@ -37,6 +37,7 @@
 #include "common.h"
 #include "hbf_taps.h"
 #include "lds_dma.h"
+#include "resample_plan.h"
 
 namespace idsp {
 namespace hbfr {
@@ -576,29 +577,17 @@ __global__ __launch_bounds__(kFmLanes *kW) void hbf_dec_ring_fm(uint32_t *st, co
 
 // -------------------------------------------------------------------------------------------------------- host
 template <int TS, int S>
-int launch_ring(uint32_t *st, const float *x, float *y, size_t lanes, size_t frames, bool lm, hipStream_t stream)
+int launch_ring(const HbfPlan &p, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames, hipStream_t stream)
 {
     using L = Lay<TS, S>;
-    if (lm) return 1;  // LaneMajor: the register-blocked kernel of hbf_blk.h (round 6)
-    if constexpr (L::rate == 16 && L::M(0) <= 4) {
-        if (lanes % kFmLanes != 0) return 1;
-        constexpr size_t bytes = size_t(kFmRows) * kFmPitch + (size_t(kFmLanes) * up4(L::words) + size_t(kSC / L::rate) * kFmTilePitch) * sizeof(float);
-        static_assert(bytes <= 160 * 1024, "one workgroup per CU");
-        if (ensure_dyn_lds<&hbf_dec_ring_fm<L>>(bytes)) return 2;
-        const size_t ngroups = lanes / kFmLanes;
-        note_kernel("hbf_dec_ring[FrameMajor]", typeid(L).name());
-        hipLaunchKernelGGL((hbf_dec_ring_fm<L>), dim3(unsigned(8 * ((ngroups + 7) / 8))), dim3(kFmLanes * kW), bytes, stream, st, x, y, lanes,
-                           frames);
-        return 0;
-    }
-    return 1;
+    static_assert(S == thr::kHbfRingStages && L::rate == 16 && L::M(0) <= 4 && kFmLanes == thr::kHbfRingLanes, "the FrameMajor ring: /16 on 16-lane groups");
+    constexpr size_t bytes = size_t(kFmRows) * kFmPitch + (size_t(kFmLanes) * up4(L::words) + size_t(kSC / L::rate) * kFmTilePitch) * sizeof(float);
+    static_assert(bytes <= 160 * 1024, "one workgroup per CU");
+    if (const int rc = ensure_dyn_lds<&hbf_dec_ring_fm<L>>(bytes)) return rc;
+    note_kernel(hbf_plan_name(p), typeid(L).name());
+    hipLaunchKernelGGL((hbf_dec_ring_fm<L>), dim3(p.grid), dim3(kFmLanes * kW), bytes, stream, st, x, y, lanes, frames);
+    return launch_status();
 }
 
 }  // namespace hbfr
-
-// Returns 0 when a ring kernel was launched, 1 when the request is not covered (the caller falls back to
-// hbf_wave.h), 2 on a HIP error (idsp_last_error() holds the text).
-int hbf_ring_dec(int tap_set, int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames,
-                 bool lane_major, hipStream_t stream);
-
 }  // namespace idsp

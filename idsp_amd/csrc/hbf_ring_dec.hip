@@ -2,19 +2,13 @@
 #include "hbf_ring.h"
 
 namespace idsp {
-namespace {
-template <int TS>
-int launch_s(int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames, bool lm, hipStream_t stream)
+int hbf_ring_launch(const HbfCall &c, const HbfPlan &p, uint32_t *st, const float *x, float *y, hipStream_t stream)
 {
-    return stages == 4 ? hbfr::launch_ring<TS, 4>(st, x, y, lanes, frames, lm, stream) : 1;
-}
-}  // namespace
-
-int hbf_ring_dec(int tap_set, int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames,
-                 bool lane_major, hipStream_t stream)
-{
-    if (tap_set == 0) return launch_s<0>(stages, st, x, y, lanes, frames, lane_major, stream);
-    if (tap_set == 1) return launch_s<1>(stages, st, x, y, lanes, frames, lane_major, stream);
-    return 1;
+    return for_cascade(c.tap_set, c.stages, [&](auto ts, auto s) {
+        if constexpr (decltype(s)::value == thr::kHbfRingStages)
+            return hbfr::launch_ring<decltype(ts)::value, decltype(s)::value>(p, st, x, y, c.lanes, c.frames, stream);
+        else
+            return fail(IDSP_EINVAL, "no %s for %d stages", hbf_plan_name(p), c.stages);
+    });
 }
 }  // namespace idsp

@@ -4,6 +4,8 @@
 // from the outermost (small) to the centre (large) tap.
 #pragma once
 
+#include "common.h"
+
 namespace idsp {
 
 constexpr int kHbfM[2][5] = {{23, 10, 5, 4, 3}, {15, 6, 3, 3, 2}};
@@ -31,5 +33,25 @@ constexpr float kHbfTaps[2][5][23] = {
 // highest-rate stage first (HBF_DEC_CASCADE, src/hbf.rs:412-421), the
 // interpolator the lowest-rate stage first (HBF_INT_CASCADE, src/hbf.rs:503-512).
 constexpr int hbf_tuple_index(bool dec, int stages, int s) { return dec ? stages - 1 - s : s; }
+
+// f(TS, S) with a built-in cascade as compile-time constants: tap set 0 / 1, 1..5 stages (the one ladder of the specialised kernels'
+// launchers: hbf_blk_dec.hip, hbf_ring_dec.hip, hbf_wave_{dec,int}.hip; plan_hbf of resample_plan.h sends nothing else there)
+template <class F>
+inline int for_cascade(int tap_set, int stages, F &&f)
+{
+    switch (tap_set == 0 || tap_set == 1 ? 10 * tap_set + stages : -1) {
+        case 1: return f(int_c<0>{}, int_c<1>{});
+        case 2: return f(int_c<0>{}, int_c<2>{});
+        case 3: return f(int_c<0>{}, int_c<3>{});
+        case 4: return f(int_c<0>{}, int_c<4>{});
+        case 5: return f(int_c<0>{}, int_c<5>{});
+        case 11: return f(int_c<1>{}, int_c<1>{});
+        case 12: return f(int_c<1>{}, int_c<2>{});
+        case 13: return f(int_c<1>{}, int_c<3>{});
+        case 14: return f(int_c<1>{}, int_c<4>{});
+        case 15: return f(int_c<1>{}, int_c<5>{});
+        default: return fail(IDSP_EINVAL, "no built-in half-band cascade: tap set %d, %d stages", tap_set, stages);
+    }
+}
 
 }  // namespace idsp

@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "hbf_taps.h"
+#include "resample_plan.h"
 
 namespace idsp {
 namespace hbfw {
@@ -664,76 +665,55 @@ __global__ __launch_bounds__(kBlkLanes *kW) void hbf_int_block_fm(uint32_t *st, 
 }
 
 // -------------------------------------------------------------------- host
-template <int TS, int S, bool DEC>
-int launch_wave(uint32_t *st, const float *x, float *y, size_t lanes, size_t frames, bool lm, hipStream_t stream)
+template <class C, bool DEC>
+constexpr auto block_fm_kernel()
 {
-    using C = Casc<TS, S, DEC>;
-    const dim3 grid{unsigned(lm ? lanes : 8 * ((lanes + 7) / 8))}, block{unsigned(kW)};
-    if (lm) {
-        if constexpr (DEC) {
-            return 1;  // LANE_MAJOR decimators: hbf_ring.h
-        } else {
-            note_kernel("hbf_int_wave[LaneMajor]", typeid(C).name());
-            hipLaunchKernelGGL((hbf_int_wave<C, true>), grid, block, 0, stream, st, x, y, lanes, frames);
-        }
-    } else {
-        if constexpr (S >= 2) {
-            if constexpr (DEC) {
-                constexpr size_t bytes = (size_t(kBlkLanes) * up4(C::lds_words) + 2 * (kCH / C::rate) * kBlkLanes) * sizeof(float);
-                static const bool use_block = !diag_env("IDSP_HBF_NO_BLOCK_FM");
-                if (use_block && bytes <= 160 * 1024 && lanes % kBlkLanes == 0) {
-                    if (ensure_dyn_lds<&hbf_dec_block_fm<C>>(bytes)) return 1;  // once per device (common.h)
-                    const size_t ngroups = lanes / kBlkLanes;
-                    note_kernel("hbf_dec_block_fm", typeid(C).name());
-                    hipLaunchKernelGGL((hbf_dec_block_fm<C>), dim3(unsigned(8 * ((ngroups + 7) / 8))), dim3(kBlkLanes * kW), bytes, stream,
-                                       st, x, y, lanes, frames);
-                    return 0;
-                }
-                note_kernel("hbf_dec_wave[FrameMajor]", typeid(C).name());
-                hipLaunchKernelGGL((hbf_dec_wave<C>), grid, block, 0, stream, st, x, y, lanes, frames);
-            }
-            else {
-                constexpr size_t bytes = (size_t(kBlkLanes) * up4(C::lds_words) + size_t(kBlkLanes) * kCH) * sizeof(float);
-                static const bool use_block = !diag_env("IDSP_HBF_NO_BLOCK_FM");
-                if (use_block && bytes <= 160 * 1024 && lanes % kBlkLanes == 0) {
-                    if (ensure_dyn_lds<&hbf_int_block_fm<C>>(bytes)) return 1;  // once per device (common.h)
-                    const size_t ngroups = lanes / kBlkLanes;
-                    note_kernel("hbf_int_block_fm", typeid(C).name());
-                    hipLaunchKernelGGL((hbf_int_block_fm<C>), dim3(unsigned(8 * ((ngroups + 7) / 8))), dim3(kBlkLanes * kW), bytes, stream,
-                                       st, x, y, lanes, frames);
-                    return 0;
-                }
-                note_kernel("hbf_int_wave[FrameMajor]", typeid(C).name());
-                hipLaunchKernelGGL((hbf_int_wave<C, false>), grid, block, 0, stream, st, x, y, lanes, frames);
-            }
-        } else {
-            return 1;  // not handled here
-        }
-    }
-    return 0;
+    if constexpr (DEC)
+        return &hbf_dec_block_fm<C>;
+    else
+        return &hbf_int_block_fm<C>;
 }
 
-template <int TS, bool DEC>
-int launch_wave_s(int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames, bool lm,
-                  hipStream_t stream)
+// BlockFm, WaveFm or WaveLm, as the plan says.  No LaneMajor decimator (hbf_blk.h) and no one-stage FrameMajor kernel exist.
+template <int TS, int S, bool DEC>
+int launch_wave(const HbfPlan &p, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames, hipStream_t stream)
 {
-    switch (stages) {
-        case 1: return launch_wave<TS, 1, DEC>(st, x, y, lanes, frames, lm, stream);
-        case 2: return launch_wave<TS, 2, DEC>(st, x, y, lanes, frames, lm, stream);
-        case 3: return launch_wave<TS, 3, DEC>(st, x, y, lanes, frames, lm, stream);
-        case 4: return launch_wave<TS, 4, DEC>(st, x, y, lanes, frames, lm, stream);
-        case 5: return launch_wave<TS, 5, DEC>(st, x, y, lanes, frames, lm, stream);
-        default: return 1;
+    using C = Casc<TS, S, DEC>;
+    static_assert(kBlkLanes == thr::kHbfBlockLanes, "plan_hbf counts the block kernels' workgroups");
+    note_kernel(hbf_plan_name(p), typeid(C).name());
+    const auto launch = [&](auto kernel, int threads, size_t bytes) {
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(threads), bytes, stream, st, x, y, lanes, frames);
+        return launch_status();
+    };
+    if constexpr (!DEC)
+        if (p.form == HbfForm::WaveLm) return launch(hbf_int_wave<C, true>, kW, 0);
+    if constexpr (S >= thr::kHbfFmMinStages) {
+        if (p.form == HbfForm::WaveFm) {
+            if constexpr (DEC)
+                return launch(hbf_dec_wave<C>, kW, 0);
+            else
+                return launch(hbf_int_wave<C, false>, kW, 0);
+        }
+        if (p.form == HbfForm::BlockFm) {
+            // the cascades of kBlkLanes lanes and the output tile: 36352 bytes at the most (the /32 decimator of tap set 0)
+            constexpr size_t tile = DEC ? 2 * size_t(kCH / C::rate) * kBlkLanes : size_t(kBlkLanes) * kCH;
+            constexpr size_t bytes = (size_t(kBlkLanes) * up4(C::lds_words) + tile) * sizeof(float);
+            static_assert(bytes <= 160 * 1024, "one workgroup per CU at least");
+            if (const int rc = ensure_dyn_lds<block_fm_kernel<C, DEC>()>(bytes)) return rc;  // once per device (common.h)
+            return launch(block_fm_kernel<C, DEC>(), kBlkLanes * kW, bytes);
+        }
     }
+    return fail(IDSP_EINVAL, "no %s for %d stages", hbf_plan_name(p), S);
+}
+
+// hbf_wave_dec.hip / hbf_wave_int.hip
+template <bool DEC>
+int launch_waves(const HbfCall &c, const HbfPlan &p, uint32_t *st, const float *x, float *y, hipStream_t stream)
+{
+    return for_cascade(c.tap_set, c.stages, [&](auto ts, auto s) {
+        return launch_wave<decltype(ts)::value, decltype(s)::value, DEC>(p, st, x, y, c.lanes, c.frames, stream);
+    });
 }
 
 }  // namespace hbfw
-
-// Returns 0 when a specialised wave kernel was launched, 1 when the request is
-// not covered (caller falls back to the generic kernels of hbf.hip).
-int hbf_wave_dec(int tap_set, int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames,
-                 bool lane_major, hipStream_t stream);
-int hbf_wave_int(int tap_set, int stages, uint32_t *st, const float *x, float *y, size_t lanes, size_t frames,
-                 bool lane_major, hipStream_t stream);
-
 }  // namespace idsp

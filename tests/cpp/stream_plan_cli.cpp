@@ -12,6 +12,11 @@
 //           biquad_lo_process, accu_process) or idsp_lockin_f32_biquad_lo_process (f32_biquad_lo_process): what idsp_last_kernel() reports —
 //           `stream_<Processor>` where launch_stream names the kernel —, a tab, `waves= groups= batch= in= skew= body= split=`
 //           (tuned: stagger_tuned_device() holds)
+//   hbf <dec|int> <tap_set|-1> <stages> <lanes> <frames> <FM|LM> <wide mod 16> [IDSP_SWITCH=value ...]
+//        -> `plan_hbf` (idsp_amd/csrc/resample_plan.h) for a call of idsp_hbf_<dec|int>_f32: the start of what idsp_last_kernel() reports
+//           (hbf_plan_name), a tab, `form= grid=`
+//   cic <dec|int> <32|64> <order> <rate> <lanes> <frames> <FM|LM> <x mod 16> <y mod 16> [IDSP_SWITCH=value ...]
+//        -> `plan_cic` for a call of idsp_cic_<dec|int>_i<32|64>: cic_plan_name, a tab, `form= ppt= vpc= grid=`
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -20,6 +25,7 @@
 #include <string>
 
 #include "../../idsp_amd/csrc/lockin_plan.h"
+#include "../../idsp_amd/csrc/resample_plan.h"
 #include "../../idsp_amd/csrc/stream_plan.h"
 
 using namespace idsp;
@@ -112,6 +118,42 @@ static bool lockin_line(std::istringstream &in, const LockinSwitches &sw, bool t
     return true;
 }
 
+// the two resampling verbs: the shape words of the line, then the switches
+template <class Env>
+static bool resample_line(const std::string &cmd, std::istringstream &in, std::map<std::string, std::string> &env, Env getenv_, std::string &out)
+{
+    std::string kind, layout, word;
+    int bits = 32;
+    HbfCall h;
+    CicCall c;
+    size_t xo = 0, yo = 0;
+    in >> kind;
+    if (cmd == "hbf")
+        in >> h.tap_set >> h.stages >> h.lanes >> h.frames >> layout >> xo;
+    else
+        in >> bits >> c.order >> c.rate >> c.lanes >> c.frames >> layout >> xo >> yo;
+    if (!in || (kind != "dec" && kind != "int") || (layout != "FM" && layout != "LM") || (bits != 32 && bits != 64)) return false;
+    while (in >> word) {
+        if (word.find('=') == std::string::npos) return false;
+        env[word.substr(0, word.find('='))] = word.substr(word.find('=') + 1);
+    }
+    char text[256];
+    if (cmd == "hbf") {
+        h.dec = kind == "dec", h.layout = layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR, h.wide = (uintptr_t(1) << 32) + xo;
+        static const char *const kForms[6] = {"Generic", "BlkLm", "RingFm", "BlockFm", "WaveFm", "WaveLm"};
+        const HbfPlan p = plan_hbf(h, read_hbf_switches(getenv_));
+        snprintf(text, sizeof text, "%s\tform=%s grid=%u", hbf_plan_name(p), kForms[int(p.form)], p.grid);
+    } else {
+        c.dec = kind == "dec", c.elem_bytes = bits / 8, c.layout = layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR;
+        c.x = (uintptr_t(1) << 32) + xo, c.y = (uintptr_t(1) << 33) + yo;
+        static const char *const kForms[4] = {"RingLm", "RingFm", "LaneTiles", "Lane"};
+        const CicPlan p = plan_cic(c, read_cic_switches(getenv_));
+        snprintf(text, sizeof text, "%s\tform=%s ppt=%d vpc=%d grid=%u", cic_plan_name(p), kForms[int(p.form)], p.ppt, p.vpc, p.grid);
+    }
+    out = text;
+    return true;
+}
+
 int main()
 {
     std::string line;
@@ -158,6 +200,12 @@ int main()
             }
             std::istringstream shape_in(shape);
             if (lockin_line(shape_in, read_lockin_switches(getenv_), tuned, entry, out))
+                printf("%s\n", out.c_str());
+            else
+                printf("error: %s\n", line.c_str());
+        } else if (cmd == "hbf" || cmd == "cic") {
+            std::string out;
+            if (resample_line(cmd, in, env, getenv_, out))
                 printf("%s\n", out.c_str());
             else
                 printf("error: %s\n", line.c_str());

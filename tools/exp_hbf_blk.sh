@@ -14,11 +14,13 @@ if [ "${1:-run}" = build ]; then
   for v in $VARIANTS; do
     n=${v%%:*}; d=${v#*:}
     /opt/rocm/bin/hipcc $FLAGS ${d//,/ } -c idsp_amd/csrc/hbf_blk_dec.hip -o $D/hbf_blk_dec_$n.o &
+    # the entry too: IDSP_HBF_BLK_OFF (WAVE) acts in read_hbf_switches (resample_plan.h), which hbf.hip compiles
+    /opt/rocm/bin/hipcc $FLAGS ${d//,/ } -c idsp_amd/csrc/hbf.hip -o $D/hbf_$n.o &
   done
   wait
   for v in $VARIANTS; do
     n=${v%%:*}
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--no-undefined -o $D/libidsp_hip_$n.so idsp_amd/csrc/hbf.o \
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--no-undefined -o $D/libidsp_hip_$n.so $D/hbf_$n.o \
       idsp_amd/csrc/hbf_wave_dec.o idsp_amd/csrc/hbf_wave_int.o idsp_amd/csrc/hbf_ring_dec.o idsp_amd/csrc/api_util.o $D/hbf_blk_dec_$n.o
   done
   ls -la $D/*.so
@@ -26,7 +28,9 @@ else
   O=gpurun_out/${OUT:-exp_hbf_blk.jsonl}; mkdir -p $(dirname $O); : > $O
   echo '{"variant": "product"}' >> $O
   python tools/perf_configs.py --only c3dec --iters ${ITERS:-10} 2>/dev/null | grep hbf_dec >> $O
-  echo '{"variant": "ring kernels of round 4 (IDSP_HBF_NO_BLK)"}' >> $O
+  # (labelled "ring kernels of round 4" when profiles/r06_exp_hbf_blk_first.jsonl was taken: the ring still served LaneMajor then.  Since
+  # hbf_ring.h and hbf_wave.h refuse LaneMajor decimators, this run is the generic kernel: plan_hbf, resample_plan.h)
+  echo '{"variant": "generic kernel (IDSP_HBF_NO_BLK)"}' >> $O
   IDSP_DIAG=1 IDSP_HBF_NO_BLK=1 python tools/perf_configs.py --only c3dec --iters ${ITERS:-10} 2>/dev/null | grep hbf_dec >> $O
   for pad in ${PADS:-1024 2048 4096}; do
     echo "{\"variant\": \"product, LaneMajor with $pad more bytes of LDS per wave\"}" >> $O
