@@ -384,6 +384,15 @@ RPLL = {
 }
 UTILS.update(RPLL)
 
+# MASH delta-sigma modulator, u32 -> i8 (product only, no twin in the checker library: parity rests on tests/_dsm_spec.py); merged
+# into UTILS the way PHASE, SWEEP and RPLL are
+DSM_MAX_ORDER = 8  # IDSP_DSM_MAX_ORDER
+DSM = {
+    "dsm_state_words": (_SZ, [_I]),
+    "dsm_u32": (_I, [_I, _P, _P, _SZ, _P, _SZ, _SZ, _SZ, _I, _P]),  # order, state, x, x_pitch, y, y_pitch, lanes, frames, layout, stream
+}
+UTILS.update(DSM)
+
 SHARD_FN = C.CFUNCTYPE(_I, _P, _I, _SZ, _SZ, _P)  # idsp_shard_fn
 
 

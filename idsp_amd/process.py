@@ -28,6 +28,7 @@ own:
     Sweep / AccuOsc<Sweep>               (sweptsine.rs:12-188) Sweep.fit(stop, harmonics, cycles), SweepOsc(N, rate, state)
     RPLLConfig / RPLL, the returned Accu (rpll.rs:13-90, accu.rs:34-54) RPLLConfig(dt2, sf, sp).lanes(N), accu_lo(accu, lo, ...),
                                                           LockinLo(...).process_accu(x, accu, y, batch_log2, harmonic)
+    Dsm<K> (u32 -> i8)                   (dsm.rs:22-57)  Dsm(K).lanes(N)   y is torch.int8
     cossin(phase)                        (cossin.rs:14)  cossin(phases)
     atan2(y, x) / Complex::arg           (atan2.rs:66)   atan2(xy)
     cordic::{cos_sin, sqrt_atan2, ...}   (cordic.rs:80-107) cordic_cos_sin(xy, z), cordic_sqrt_atan2(xy, z), ...
@@ -52,7 +53,7 @@ __all__ = [
     "FrameMajor", "LaneMajor", "View", "ViewMut", "Biquad", "BiquadClamp", "Cascade",
     "DirectForm1", "DirectForm2Transposed", "DirectForm1Wide", "DirectForm1Dither", "DirectForm",
     "Split", "Lanes", "ByLane", "HbfDecCascade", "HbfIntCascade", "FirSym", "Cic", "Normal", "Wdf", "HBF_TAPS", "HBF_TAPS_98",
-    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "Sweep", "SweepOsc", "FmDisc", "PLL", "RPLLConfig", "RPLLLanes", "accu_lo", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
+    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "Sweep", "SweepOsc", "FmDisc", "PLL", "RPLLConfig", "RPLLLanes", "accu_lo", "Dsm", "DsmLanes", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
     "cordic_circular_gain", "cordic_hyperbolic_gain", "sos", "sos_clamp_wide", "IdspError",
 ]
 
@@ -1197,6 +1198,49 @@ class ClampWrapLanes(_LaneOp):
     def _run(self, x, y, frames, layout):
         call("clamp_wrap_i32", C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
              self.n_lanes, frames, layout, _stream_ptr(x))
+
+
+class Dsm:
+    """`Dsm<K>` (src/dsm.rs:22-26), the MASH-(1)^K delta-sigma modulator, `order` = K in 0..=8.  `.lanes(n)` gives the per-lane
+    `Dsm::default()` states."""
+
+    def __init__(self, order: int):
+        if isinstance(order, bool) or not isinstance(order, int) or not 0 <= order <= _abi.DSM_MAX_ORDER:
+            raise ValueError(f"order must be an integer in 0..={_abi.DSM_MAX_ORDER}")
+        self.order = order
+
+    def lanes(self, n: int, device="cuda") -> "DsmLanes":
+        return DsmLanes(self, n, device)
+
+
+class DsmLanes(_LaneOp):
+    """`Dsm::<K>::process` per lane (src/dsm.rs:44-57, release-build wrapping): x is int32 carrying the u32 bits, y is int8, one byte
+    per sample.  `.state` is `[2 * order, n]`: rows 0..K-1 are `a`, rows K..2K-1 are `c` (read as their low byte).  Dense tensors only
+    (the row pitches of idsp_dsm_u32 are for callers of the C ABI); there is no in-place form: x and y differ in element size."""
+
+    dtype_out = torch.int8
+
+    def __init__(self, dsm: Dsm, n_lanes: int, device="cuda"):
+        if int(n_lanes) < 0:
+            raise ValueError("lanes must be >= 0")
+        if torch.device(device).type != "cuda":
+            raise ValueError("idsp_amd runs on the GPU only")
+        self.order = dsm.order
+        super().__init__(n_lanes, 2 * dsm.order, device)
+
+    def _run(self, x, y, frames, layout):
+        if x.device != self.state.device or y.device != self.state.device:
+            raise ValueError("x and y must be on the device of the state")
+        if frames == 0 or self.n_lanes == 0:
+            return  # empty tensors have no data pointer
+        call("dsm_u32", self.order, C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()), 0, C.c_void_p(y.data_ptr()), 0,
+             self.n_lanes, frames, layout, _stream_ptr(x))
+
+    def inplace(self, xy):
+        raise ValueError("Dsm has no in-place form: x is u32 and y is i8")
+
+    def inplace_view(self, xy):
+        raise ValueError("Dsm has no in-place form: x is u32 and y is i8")
 
 
 class PolyphaseBank(_LaneOp):

@@ -1027,6 +1027,41 @@ int idsp_lockin_i32_accu_process(const idsp_lockin_i32 *cfg, const idsp_accu_lo 
                                  const int32_t *accu, int32_t *y, size_t lanes, size_t updates, int layout, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Dsm<K> — MASH-(1)^K delta-sigma modulator, u32 -> i8 (src/dsm.rs)        */
+/* ------------------------------------------------------------------------ */
+/*
+ * `Dsm::<K>::process(x: u32) -> i8` (src/dsm.rs:44-57) per lane, K = `order` = 0..IDSP_DSM_MAX_ORDER: the output stage of the
+ * reference, a 32-bit word in, the small integer a DAC, PWM or fractional-N divider consumes out.  The only entry whose output
+ * element is smaller than a 32-bit word: y holds plain i8 rows, ONE BYTE per sample, in `layout`.
+ * Computed as a RELEASE build of the reference computes it — every u32 and i8 operation wraps:
+ *   stage fold (:47-51)          a[i], carry[i] = a[i].overflowing_add(v); v = x for stage 0, the new a[i-1] after it
+ *   recombination fold (:52-56)  y = carry[K-1]; for j = 0..K-2: (y, c[j]) = (carry[K-2-j] + y - c[j], y), wrapping i8
+ * What the reference leaves open and this ABI fixes:
+ *   - from `Dsm::default()` no i8 operation overflows and the output stays inside 1 - 2^(K-1) ..= 2^(K-1); from arbitrary c
+ *     words the second fold overflows i8 already at K = 3, where a debug build of the reference panics.  Here it wraps;
+ *   - K = 1: the output is the carry.  K = 0: the output is the constant 0 (what the release build yields and the doc comment
+ *     promises), there is no state and `state` may be NULL;
+ *   - c[K-1] is a field of the struct that `process` never reads or writes (`take(K - 1)`).
+ * State: 2 K words per lane, word-plane-major as everywhere: words 0..K-1 = a[0..K-1], words K..2K-1 = c[0..K-1].  A c word is
+ * read as its low byte (`(int8_t)w`) and written back sign-extended; word 2K-1 is never written.  All zero is `Dsm::default()`.
+ * Read at entry, written at exit; FRAME_MAJOR and LANE_MAJOR calls may be mixed on one state.
+ * x_pitch / y_pitch: ELEMENTS between the starts of consecutive rows (frames in FRAME_MAJOR, lanes in LANE_MAJOR) of x and of
+ * y, as the `_pitch` twins above define them; 0 = dense.  They belong to the one entry: i8 rows with an odd row length are the
+ * normal case, and the pitch is how a caller keeps them aligned.  x must be 4-byte aligned; y may start at ANY byte and
+ * y_pitch may be any value >= a row.  Bytes of y outside the `lanes` x `frames` elements (the gap of a pitched row) are not
+ * written.  LANE_MAJOR rows aligned to 4 bytes (y and y_pitch multiples of 4) leave through dword stores, in about half the time of
+ * unaligned ones (profiles/NOTES.md, "Dsm"); FRAME_MAJOR stores bytes whatever the alignment.
+ * There is no in-place form (the elements differ in size): any overlap of the two extents, (rows-1) * pitch + row elements
+ * each, is IDSP_EINVAL.  Also IDSP_EINVAL, with nothing written: an order outside 0..8, a bad layout, NULL x or y, NULL state
+ * with order > 0, a pitch shorter than a row.  lanes == 0 or frames == 0 is IDSP_OK and writes nothing.
+ * Asynchronous on `stream`; no host synchronisation, no allocation.
+ */
+#define IDSP_DSM_MAX_ORDER 8
+size_t idsp_dsm_state_words(int order); /* 2 * order; 0 for an order outside 0..IDSP_DSM_MAX_ORDER */
+int idsp_dsm_u32(int order, void *state, const uint32_t *x, size_t x_pitch, int8_t *y, size_t y_pitch,
+                 size_t lanes, size_t frames, int layout, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* lane split over several devices in ONE process: idsp_multi_*             */
 /* ------------------------------------------------------------------------ */
 /*

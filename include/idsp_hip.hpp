@@ -1349,4 +1349,51 @@ struct AccuLo {
     }
 };
 
+// ------------------------------------------------ delta-sigma modulator
+class DsmLanes;
+/// `Dsm<K>` (src/dsm.rs:22-26), the MASH-(1)^K delta-sigma modulator with a runtime `order` = K in 0..=IDSP_DSM_MAX_ORDER.
+struct Dsm {
+    int order;
+    explicit Dsm(int order_) : order(order_) { require(order >= 0 && order <= IDSP_DSM_MAX_ORDER, "order must be in 0..=8"); }
+    inline DsmLanes lanes(size_t n, void *stream = nullptr) const;
+};
+
+/// `Dsm::<K>::process` per lane (src/dsm.rs:44-57, release-build wrapping; idsp_dsm_u32): u32 in, i8 out, one byte per sample.
+/// Zero state = `Dsm::default()`; state words 0..K-1 are `a`, K..2K-1 are `c`.  No in-place form: x and y differ in element size.
+class DsmLanes {
+public:
+    DsmLanes(const Dsm &dsm, size_t lanes, void *stream = nullptr)
+        : order_(dsm.order), lanes_(lanes), stream_(stream), state_(idsp_dsm_state_words(dsm.order) * lanes)
+    {
+    }
+    DeviceBuffer<uint32_t> &state() { return state_; }
+    int order() const { return order_; }
+    /// back to `Dsm::default()` in every lane
+    void reset()
+    {
+        if (state_.len()) check(idsp_device_memset(state_.data(), 0, state_.len() * sizeof(uint32_t), stream_));
+    }
+    /// x_pitch / y_pitch: elements between the starts of consecutive rows of x / y (frames in FrameMajor, lanes in LaneMajor), 0 =
+    /// dense; a view of pitched rows is built by hand (`View{ptr, frames, lanes}`), `from_flat` describes dense ones.  y may start at
+    /// any byte; LaneMajor rows of y aligned to 4 bytes (y and y_pitch multiples of 4) are the fast case.
+    template <class Layout>
+    void process_view(View<uint32_t, Layout> x, ViewMut<int8_t, Layout> y, size_t x_pitch = 0, size_t y_pitch = 0)
+    {
+        require(x.frames == y.frames && x.lanes == lanes_ && y.lanes == lanes_, "view shape mismatch");
+        const size_t row = Layout::value == IDSP_LANE_MAJOR ? x.frames : lanes_;
+        require((!x_pitch || x_pitch >= row) && (!y_pitch || y_pitch >= row), "pitch shorter than a row");
+        if (lanes_ == 0 || x.frames == 0) return;
+        check(idsp_dsm_u32(order_, state_.data(), x.flat, x_pitch, y.flat, y_pitch, lanes_, x.frames, Layout::value, stream_));
+    }
+    /// `Process::block` over `&[[u32; N]]`: FrameMajor
+    void block(View<uint32_t, FrameMajor> x, ViewMut<int8_t, FrameMajor> y, size_t x_pitch = 0, size_t y_pitch = 0) { process_view(x, y, x_pitch, y_pitch); }
+
+private:
+    int order_;
+    size_t lanes_;
+    void *stream_;
+    DeviceBuffer<uint32_t> state_;
+};
+inline DsmLanes Dsm::lanes(size_t n, void *stream) const { return DsmLanes(*this, n, stream); }
+
 }  // namespace idsp_hip
