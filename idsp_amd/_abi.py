@@ -393,6 +393,26 @@ DSM = {
 }
 UTILS.update(DSM)
 
+
+# `Biquad<Q16<F>>` / `BiquadClamp<Q16<F>, i16>` on i16 rows (product only, no twin in the checker library: parity rests on
+# tests/_biquad_i16_spec.py, pinned by oracle/spec.py: biquad_i32_df1); merged into UTILS the way DSM is
+class BiquadI16(C.Structure):
+    _fields_ = [("ba", C.c_int16 * 5), ("frac", C.c_int16)]
+
+
+class BiquadClampI16(C.Structure):
+    _fields_ = [("ba", C.c_int16 * 5), ("frac", C.c_int16), ("u", C.c_int16), ("min", C.c_int16), ("max", C.c_int16)]
+
+
+BIQUAD_I16 = {
+    "biquad_i16_from_sos": (_I, [_P, _I, _P]),  # sos, frac, out
+    "biquad_i16_state_words": (_SZ, [_SZ]),
+    # cfg, n, state, x, x_pitch, y, y_pitch, lanes, frames, layout, stream
+    "biquad_i16_df1": (_I, [_P, _SZ, _P, _P, _SZ, _P, _SZ, _SZ, _SZ, _I, _P]),
+    "biquad_i16_df1_clamp": (_I, [_P, _SZ, _P, _P, _SZ, _P, _SZ, _SZ, _SZ, _I, _P]),
+}
+UTILS.update(BIQUAD_I16)
+
 SHARD_FN = C.CFUNCTYPE(_I, _P, _I, _SZ, _SZ, _P)  # idsp_shard_fn
 
 

@@ -29,6 +29,7 @@ own:
     RPLLConfig / RPLL, the returned Accu (rpll.rs:13-90, accu.rs:34-54) RPLLConfig(dt2, sf, sp).lanes(N), accu_lo(accu, lo, ...),
                                                           LockinLo(...).process_accu(x, accu, y, batch_log2, harmonic)
     Dsm<K> (u32 -> i8)                   (dsm.rs:22-57)  Dsm(K).lanes(N)   y is torch.int8
+    Biquad<Q16<F>> / BiquadClamp<Q16<F>, i16> (iir/biquad.rs:366-404) BiquadQ16(ba, frac=F[, u, min, max]).lanes(N)   x, y are torch.int16
     cossin(phase)                        (cossin.rs:14)  cossin(phases)
     atan2(y, x) / Complex::arg           (atan2.rs:66)   atan2(xy)
     cordic::{cos_sin, sqrt_atan2, ...}   (cordic.rs:80-107) cordic_cos_sin(xy, z), cordic_sqrt_atan2(xy, z), ...
@@ -53,7 +54,7 @@ __all__ = [
     "FrameMajor", "LaneMajor", "View", "ViewMut", "Biquad", "BiquadClamp", "Cascade",
     "DirectForm1", "DirectForm2Transposed", "DirectForm1Wide", "DirectForm1Dither", "DirectForm",
     "Split", "Lanes", "ByLane", "HbfDecCascade", "HbfIntCascade", "FirSym", "Cic", "Normal", "Wdf", "HBF_TAPS", "HBF_TAPS_98",
-    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "Sweep", "SweepOsc", "FmDisc", "PLL", "RPLLConfig", "RPLLLanes", "accu_lo", "Dsm", "DsmLanes", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
+    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "Sweep", "SweepOsc", "FmDisc", "PLL", "RPLLConfig", "RPLLLanes", "accu_lo", "Dsm", "DsmLanes", "BiquadQ16", "BiquadQ16Lanes", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
     "cordic_circular_gain", "cordic_hyperbolic_gain", "sos", "sos_clamp_wide", "IdspError",
 ]
 
@@ -1241,6 +1242,76 @@ class DsmLanes(_LaneOp):
 
     def inplace_view(self, xy):
         raise ValueError("Dsm has no in-place form: x is u32 and y is i8")
+
+
+class BiquadQ16:
+    """`Biquad<Q16<F>>` (src/iir/biquad.rs:96-116 with C = Q<i16, i32, F>): ba = [b0, b1, b2, a1, a2] as raw i16 bits, a1/a2 stored as
+    used, `frac` = F in 0..=31 (the shift of the i32 accumulator).  With any of `u`, `min`, `max` it is `BiquadClamp<Q16<F>, i16>`
+    (:121-157; the missing ones default to 0, i16::MIN, i16::MAX).  `.lanes(n)`, or `BiquadQ16Lanes([c0, c1, ..], n)` for a serial
+    chain, gives the per-lane `DirectForm1<i16>` states."""
+
+    def __init__(self, ba: Sequence[int], frac: int, u: Optional[int] = None, min: Optional[int] = None, max: Optional[int] = None):
+        if len(ba) != 5:
+            raise ValueError("ba must hold 5 coefficients")
+        if isinstance(frac, bool) or not isinstance(frac, int) or not 0 <= frac <= 31:
+            raise ValueError("frac must be an integer in 0..=31")
+        self.clamp = not (u is None and min is None and max is None)
+        self.u, self.min, self.max = (0 if u is None else int(u)), (-32768 if min is None else int(min)), (32767 if max is None else int(max))
+        self.ba, self.frac = [int(v) for v in ba], frac
+        if any(not -32768 <= v <= 32767 for v in self.ba + [self.u, self.min, self.max]):
+            raise ValueError("coefficients, u, min and max are i16")
+
+    @classmethod
+    def from_sos(cls, sos: Sequence[float], frac: int, **clamp) -> "BiquadQ16":
+        """`Biquad::from([[b0,b1,b2],[a0,a1,a2]])` (src/iir/biquad.rs:545-566), quantised like `f64 -> Q16<F>`: round half away from
+        zero, saturating, NaN -> 0 (dsp-fixedpoint/src/num_traits_impl.rs:32-46); idsp_biquad_i16_from_sos"""
+        if len(sos) != 6:
+            raise ValueError("sos must hold [b0, b1, b2, a0, a1, a2]")
+        load()
+        out = _abi.BiquadI16()
+        call("biquad_i16_from_sos", (C.c_double * 6)(*[float(v) for v in sos]), frac, C.byref(out))
+        return cls(list(out.ba), int(out.frac), **clamp)
+
+    def lanes(self, n: int, device="cuda") -> "BiquadQ16Lanes":
+        return BiquadQ16Lanes([self], n, device)
+
+
+class BiquadQ16Lanes(_LaneOp):
+    """`Biquad<Q16<F>>` / `BiquadClamp<Q16<F>, i16>` x `DirectForm1<i16>` per lane (src/iir/biquad.rs:366-404, release-build wrapping;
+    idsp_biquad_i16_df1 / _df1_clamp): x and y are torch.int16, one element per sample; `sections` run in series (`[C] x [S]`,
+    compose.rs:43-77; all plain or all clamped).  `.state` is `[4 * len(sections), n]` int32: rows {x0, x1, y0, y1} per section, each
+    read as its low half.  `inplace` is the reference's.  Dense tensors only (the row pitches of the entry are for callers of the C
+    ABI): LaneMajor rows with an even length on 4-byte-aligned tensors take the fast kernel."""
+
+    dtype_in = dtype_out = torch.int16
+
+    def __init__(self, sections: Sequence[BiquadQ16], n_lanes: int, device="cuda"):
+        sections = list(sections)
+        if int(n_lanes) < 0:
+            raise ValueError("lanes must be >= 0")
+        if torch.device(device).type != "cuda":
+            raise ValueError("idsp_amd runs on the GPU only")
+        if len(sections) > _abi.MAX_SECTIONS or any(not isinstance(s, BiquadQ16) for s in sections):
+            raise ValueError(f"sections: at most {_abi.MAX_SECTIONS} BiquadQ16")
+        if len({s.clamp for s in sections}) > 1:
+            raise ValueError("sections must be all Biquad or all BiquadClamp")
+        self.clamp = bool(sections) and sections[0].clamp
+        self._cfg = ((_abi.BiquadClampI16 if self.clamp else _abi.BiquadI16) * max(len(sections), 1))()
+        for a, s in zip(self._cfg, sections):
+            a.ba[:] = s.ba
+            a.frac = s.frac
+            if self.clamp:
+                a.u, a.min, a.max = s.u, s.min, s.max
+        self._n = len(sections)
+        super().__init__(n_lanes, 4 * self._n, device)
+
+    def _run(self, x, y, frames, layout):
+        if x.device != self.state.device or y.device != self.state.device:
+            raise ValueError("x and y must be on the device of the state")
+        if frames == 0 or self.n_lanes == 0:
+            return  # empty tensors have no data pointer
+        call("biquad_i16_df1_clamp" if self.clamp else "biquad_i16_df1", self._cfg, self._n, C.c_void_p(self.state.data_ptr()),
+             C.c_void_p(x.data_ptr()), 0, C.c_void_p(y.data_ptr()), 0, self.n_lanes, frames, layout, _stream_ptr(x))
 
 
 class PolyphaseBank(_LaneOp):

@@ -222,6 +222,73 @@ int idsp_cascade_i32_df1(const idsp_biquad_i32 *cfg, size_t n, void *state,
                          int layout, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* iir::Biquad — 16-bit fixed point, i16 rows (src/iir/biquad.rs)           */
+/* ------------------------------------------------------------------------ */
+/*
+ * `Biquad<Q16<F>>` x `DirectForm1<i16>`: the generic impl of src/iir/biquad.rs:366-383 with C = Q<i16, i32, F>, T = i16,
+ * A = Q<i32, i16, F> — the same per-lane recurrence as idsp_biquad_i32_df1 on half the bytes in and half the bytes out.  x and y
+ * hold plain i16 rows, ONE ELEMENT per sample, in `layout`.  Computed as a RELEASE build of the reference computes it — every i32
+ * and i16 operation wraps:
+ *   acc: i32 = b0*x0 + b1*x[0] + b2*x[1] + a1*y[0] + a2*y[1]   each product i32(c) * i32(v) (dsp-fixedpoint/src/lib.rs:310-312,
+ *                                                              ops.rs:91-97), the sum left to right in wrapping i32
+ *                                                              (ops.rs:63-76).  Five products of up to 2^30 do leave i32: a
+ *                                                              debug build panics there, here the sum wraps;
+ *   y0 = (acc >> F) as i16                                     arithmetic shift of the i32, truncating cast
+ *                                                              (num_traits_impl.rs:74-90, lib.rs:270-299);
+ *   x = [x0, x[0]]; y = [y0, y[0]]                             (biquad.rs:379-380).
+ * `BiquadClamp<Q16<F>, i16>` (biquad.rs:394-404): y0 = clamp(process(..) + u, min, max), the `+` in wrapping i16, `num_traits::clamp`
+ * (a value below min yields min, else one above max yields max, also when min > max), then state.y[0] = y0.
+ * frac = F, 0 <= F < 32, is the shift of the i32 accumulator: the rule of idsp_biquad_i32.
+ */
+typedef struct idsp_biquad_i16 {
+    int16_t ba[5]; /* [b0,b1,b2,a1,a2] raw Q bits, a1,a2 exactly as used in the recurrence */
+    int16_t frac;
+} idsp_biquad_i16; /* 12 bytes */
+
+typedef struct idsp_biquad_clamp_i16 {
+    int16_t ba[5];
+    int16_t frac;
+    int16_t u;   /* summing junction offset */
+    int16_t min; /* lower limit */
+    int16_t max; /* upper limit */
+} idsp_biquad_clamp_i16; /* 18 bytes */
+
+/* `From<[[f64;3];2]> for Biquad<C>` (src/iir/biquad.rs:545-566) followed by `round(v * 2^F)`, half away from zero, saturating to
+ * i16, NaN -> 0 (dsp-fixedpoint/src/num_traits_impl.rs:32-46).  Host code.  IDSP_EINVAL: NULL sos / out, frac outside 0..31. */
+int idsp_biquad_i16_from_sos(const double sos[6], int frac, idsp_biquad_i16 *out);
+
+/*
+ * n serial sections, 0 <= n <= IDSP_MAX_SECTIONS, as for every idsp_biquad_* entry; n == 0 copies x to y and leaves the state
+ * alone (compose.rs:63-65).  Up to four sections run in one launch; longer chains run as further passes in place on y (the
+ * reference's slice composition, compose.rs:43-77).
+ * State: W = 4 words per section and lane { x0, x1, y0, y1 } (biquad.rs:260-269,319), word-plane-major as everywhere, section s
+ * owning words [4 s, 4 s + 4).  Each i16 sits in a 32-bit word that is read as its low half (`(int16_t)w`) and written back
+ * sign-extended.  All zero is `Default::default()`.  Read at entry, written at exit; FRAME_MAJOR and LANE_MAJOR calls may be
+ * mixed on one state.
+ * x_pitch / y_pitch: ELEMENTS between the starts of consecutive rows (frames in FRAME_MAJOR, lanes in LANE_MAJOR), 0 = dense.
+ * They belong to the one entry (there is no `_pitch` twin): i16 rows with an odd length are the normal case, and the pitch is how
+ * a caller keeps them on the 4-byte grid.  x and y may start at any 2-BYTE-aligned address and any pitch >= a row is accepted;
+ * elements of y in the gap of a pitched row are not written.  FRAME_MAJOR has one kernel form, a lane per thread on 16-bit accesses,
+ * whatever the alignment.  LANE_MAJOR has a fast form that needs every row of x and y on the 4-byte grid — x and y 4-byte
+ * aligned and both pitches (or dense row lengths) even; an odd frame count is fine —: then a thread moves a dword, two
+ * consecutive frames of a lane.  Every other LANE_MAJOR call runs on 16-bit accesses, correct and slower (profiles/NOTES.md,
+ * "Biquad i16").
+ * In place: y == x with y_pitch == x_pitch is allowed (0 counting as the row length) — the reference's `inplace()`
+ * (biquad.rs:540-541).  Any other overlap of the two extents, (rows-1) * pitch + row elements each, is IDSP_EINVAL.
+ * Also IDSP_EINVAL, with nothing written: a bad layout, n > IDSP_MAX_SECTIONS, NULL cfg with n > 0, NULL state with n > 0 and
+ * lanes > 0, NULL x or y with lanes, frames > 0, a frac outside 0..31, a pitch shorter than a row, an odd x or y address, an
+ * extent past size_t.  lanes == 0 or frames == 0 is IDSP_OK and writes nothing.
+ * Asynchronous on `stream`; no host synchronisation, no allocation.
+ */
+size_t idsp_biquad_i16_state_words(size_t n); /* 4 * n */
+/* `Biquad<Q16<F>>` x `DirectForm1<i16>` (src/iir/biquad.rs:366-383). */
+int idsp_biquad_i16_df1(const idsp_biquad_i16 *cfg, size_t n, void *state, const int16_t *x, size_t x_pitch,
+                        int16_t *y, size_t y_pitch, size_t lanes, size_t frames, int layout, void *stream);
+/* `BiquadClamp<Q16<F>, i16>` x `DirectForm1<i16>` (src/iir/biquad.rs:394-404). */
+int idsp_biquad_i16_df1_clamp(const idsp_biquad_clamp_i16 *cfg, size_t n, void *state, const int16_t *x, size_t x_pitch,
+                              int16_t *y, size_t y_pitch, size_t lanes, size_t frames, int layout, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* iir::Biquad — f32                                                        */
 /* ------------------------------------------------------------------------ */
 

@@ -1396,4 +1396,69 @@ private:
 };
 inline DsmLanes Dsm::lanes(size_t n, void *stream) const { return DsmLanes(*this, n, stream); }
 
+// ------------------------------------------------ 16-bit fixed-point biquad
+/// `Biquad<Q16<F>>` from `[[b0,b1,b2],[a0,a1,a2]]` (src/iir/biquad.rs:545-566, idsp_biquad_i16_from_sos)
+inline idsp_biquad_i16 biquad_i16_from_sos(const double (&sos)[6], int frac)
+{
+    idsp_biquad_i16 out{};
+    check(idsp_biquad_i16_from_sos(sos, frac, &out));
+    return out;
+}
+
+/// `Biquad<Q16<F>>` (Cfg = idsp_biquad_i16) or `BiquadClamp<Q16<F>, i16>` (Cfg = idsp_biquad_clamp_i16) x `DirectForm1<i16>` per lane
+/// (src/iir/biquad.rs:366-404, release-build wrapping; idsp_biquad_i16_df1 / _df1_clamp): i16 rows in and out, `sections` in series.
+/// Zero state = `Default::default()`; state words {x0, x1, y0, y1} per section, each read as its low half.
+template <class Cfg>
+class BiquadI16Lanes {
+    static_assert(std::is_same<Cfg, idsp_biquad_i16>::value || std::is_same<Cfg, idsp_biquad_clamp_i16>::value, "Cfg: idsp_biquad_i16 or idsp_biquad_clamp_i16");
+
+public:
+    BiquadI16Lanes(std::vector<Cfg> sections, size_t lanes, void *stream = nullptr)
+        : cfg_(std::move(sections)), lanes_(lanes), stream_(stream), state_(idsp_biquad_i16_state_words(checked(cfg_)) * lanes)
+    {
+    }
+    DeviceBuffer<uint32_t> &state() { return state_; }
+    size_t sections() const { return cfg_.size(); }
+    /// back to `Default::default()` in every lane
+    void reset()
+    {
+        if (state_.len()) check(idsp_device_memset(state_.data(), 0, state_.len() * sizeof(uint32_t), stream_));
+    }
+    /// x_pitch / y_pitch: elements between the starts of consecutive rows of x / y (frames in FrameMajor, lanes in LaneMajor), 0 =
+    /// dense; a view of pitched rows is built by hand (`View{ptr, frames, lanes}`).  x and y may start at any 2-byte-aligned address;
+    /// LaneMajor rows on the 4-byte grid are the fast case.  y.flat == x.flat with one pitch is in place.
+    template <class Layout>
+    void process_view(View<int16_t, Layout> x, ViewMut<int16_t, Layout> y, size_t x_pitch = 0, size_t y_pitch = 0)
+    {
+        require(x.frames == y.frames && x.lanes == lanes_ && y.lanes == lanes_, "view shape mismatch");
+        const size_t row = Layout::value == IDSP_LANE_MAJOR ? x.frames : lanes_;
+        require((!x_pitch || x_pitch >= row) && (!y_pitch || y_pitch >= row), "pitch shorter than a row");
+        if (lanes_ == 0 || x.frames == 0) return;
+        if constexpr (std::is_same<Cfg, idsp_biquad_i16>::value)
+            check(idsp_biquad_i16_df1(cfg_.data(), cfg_.size(), state_.data(), x.flat, x_pitch, y.flat, y_pitch, lanes_, x.frames, Layout::value, stream_));
+        else
+            check(idsp_biquad_i16_df1_clamp(cfg_.data(), cfg_.size(), state_.data(), x.flat, x_pitch, y.flat, y_pitch, lanes_, x.frames, Layout::value, stream_));
+    }
+    /// `Process::block` over `&[[i16; N]]`: FrameMajor
+    void block(View<int16_t, FrameMajor> x, ViewMut<int16_t, FrameMajor> y, size_t x_pitch = 0, size_t y_pitch = 0) { process_view(x, y, x_pitch, y_pitch); }
+    /// `Inplace::inplace` / `ViewInplace::inplace_view` (biquad.rs:540-541)
+    template <class Layout>
+    void inplace_view(ViewMut<int16_t, Layout> xy, size_t pitch = 0)
+    {
+        process_view(View<int16_t, Layout>{xy.flat, xy.frames, xy.lanes}, xy, pitch, pitch);
+    }
+
+private:
+    static size_t checked(const std::vector<Cfg> &c)
+    {
+        require(c.size() <= IDSP_MAX_SECTIONS, "at most IDSP_MAX_SECTIONS sections");
+        for (const Cfg &s : c) require(s.frac >= 0 && s.frac <= 31, "frac must be in 0..=31");
+        return c.size();
+    }
+    std::vector<Cfg> cfg_;
+    size_t lanes_;
+    void *stream_;
+    DeviceBuffer<uint32_t> state_;
+};
+
 }  // namespace idsp_hip

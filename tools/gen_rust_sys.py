@@ -20,9 +20,10 @@ HEADER = os.path.join(ROOT, "include", "idsp_hip.h")
 OUT = os.path.join(ROOT, "rust", "idsp-hip-sys", "src", "lib.rs")
 # Configuration structs that live in a module of their own (src/<module>.rs, re-exported from lib.rs).  tests/test_rust_shim.py
 # pins the list of `pub struct`s of lib.rs itself to the ctypes classes it knows; a struct added to the header later goes here, and
-# the test that comes with it (tests/test_pfb_spec.py for `pfb`, tests/test_rpll_spec.py for `rpll`) holds its size against ctypes the
+# the test that comes with it (tests/test_pfb_spec.py for `pfb`, tests/test_rpll_spec.py for `rpll`, tests/test_biquad_i16_host.py for
+# `biquad_i16`) holds its size against ctypes the
 # same way.
-SIDE_MODULES = {"idsp_pfb_f32": "pfb", "idsp_rpll": "rpll", "idsp_accu_lo": "rpll"}
+SIDE_MODULES = {"idsp_pfb_f32": "pfb", "idsp_rpll": "rpll", "idsp_accu_lo": "rpll", "idsp_biquad_i16": "biquad_i16", "idsp_biquad_clamp_i16": "biquad_i16"}
 
 SCALARS = {
     "int": "c_int", "unsigned": "c_uint", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",

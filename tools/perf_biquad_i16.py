@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Time idsp_biquad_i16_df1 on an MI355X against idsp_biquad_i32_df1 (a plain tool, not a test; profiles/NOTES.md, "Biquad i16").
+
+  python tools/perf_biquad_i16.py [--out FILE.jsonl] [--lanes 65536 16384] [--frames 4096] [--sections 1] [--label TEXT]
+
+Per shape (65536 and 16384 lanes x 4096 frames) and layout, one low-pass section: the i32 call, the i16 call and the i16 call in place,
+INTERLEAVED round by round in one process (whatever else the box does hits all three): HIP-event time of 100 calls after 5 warm-ups,
+seven rounds, the median reported with the minimum and maximum — for the i32 comparator too, so that its spread stands beside every
+ratio.  The i16 call moves 4 bytes per sample (2 in, 2 out), the i32 call 8: `peak` is the i16 call's own bytes over its time as a
+fraction of the 8 TB/s HBM peak, `time_over_i32` the ratio t_i16 / t_i32 (0.5 where both are memory-bound).
+The kernel form is the library's choice (idsp_last_kernel() is recorded); to time another FrameMajor workgroup size run the tool again
+under IDSP_DIAG=1 with IDSP_BQ16_FM_BLOCK=64 / 128 / 256 (read once per process) and give the run a --label.
+One JSON line per measurement; needs a GPU (no fallback)."""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+WARMUP, CALLS, ROUNDS = 5, 100, 7
+HBM_PEAK = 8.0e12  # bytes / s
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--lanes", type=int, nargs="+", default=[65536, 16384])
+    ap.add_argument("--frames", type=int, default=4096)
+    ap.add_argument("--sections", type=int, default=1)
+    ap.add_argument("--label", default="default")
+    args = ap.parse_args()
+
+    import torch
+
+    from idsp_amd import _abi
+    from idsp_amd._lib import load
+
+    if not torch.cuda.is_available():
+        print("perf_biquad_i16: no GPU", file=sys.stderr)
+        return 2
+    fn, _ = load()
+    dev = "cuda:0"
+    out = open(args.out, "a") if args.out else None
+
+    def emit(rec):
+        rec = dict(label=args.label, **rec)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr())
+
+    def timed(call):
+        for _ in range(WARMUP):
+            assert call() == 0, fn["last_error"]()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(CALLS):
+            call()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / CALLS
+
+    ns = args.sections
+    lp = (C.c_double * 6)(0.06745527388907189, 0.13491054777814377, 0.06745527388907189, 1.0, -1.1429805025399011, 0.4128015980961886)  # low-pass, f0 = 0.1
+    c16, c32 = (_abi.BiquadI16 * ns)(), (_abi.BiquadI32 * ns)()
+    for k in range(ns):
+        assert fn["biquad_i16_from_sos"](lp, 13, C.byref(c16[k])) == 0 and fn["biquad_i32_from_sos"](lp, 29, C.byref(c32[k])) == 0
+
+    emit({"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "calls": CALLS, "rounds": ROUNDS, "frames": args.frames, "sections": ns,
+          "switches": {k: v for k, v in os.environ.items() if k.startswith("IDSP_")}})
+    for lanes in args.lanes:
+        frames = args.frames
+        n = lanes * frames
+        g = torch.Generator(device=dev).manual_seed(lanes)
+        x16 = torch.randint(-12000, 12001, (n,), dtype=torch.int16, device=dev, generator=g)
+        x32 = torch.randint(-(1 << 24), 1 << 24, (n,), dtype=torch.int32, device=dev, generator=g)
+        y16, xy16, y32 = torch.empty_like(x16), x16.clone(), torch.empty_like(x32)
+        for layout, lname in ((_abi.FRAME_MAJOR, "FrameMajor"), (_abi.LANE_MAJOR, "LaneMajor")):
+            s16, s16i, s32 = (torch.zeros((4 * ns, lanes), dtype=torch.int32, device=dev) for _ in range(3))
+            calls = {
+                "biquad_i32_df1": lambda: fn["biquad_i32_df1"](c32, ns, ptr(s32), ptr(x32), ptr(y32), lanes, frames, layout, None),
+                "biquad_i16_df1": lambda: fn["biquad_i16_df1"](c16, ns, ptr(s16), ptr(x16), 0, ptr(y16), 0, lanes, frames, layout, None),
+                "biquad_i16_df1 in place": lambda: fn["biquad_i16_df1"](c16, ns, ptr(s16i), ptr(xy16), 0, ptr(xy16), 0, lanes, frames, layout, None),
+            }
+            ms, kernels = {k: [] for k in calls}, {}
+            for _ in range(ROUNDS):
+                for k, call in calls.items():
+                    ms[k].append(timed(call))
+                    kernels[k] = fn["last_kernel"]().decode()
+            ref = statistics.median(ms["biquad_i32_df1"])
+            for k in calls:
+                med, bps = statistics.median(ms[k]), (8 if k == "biquad_i32_df1" else 4)
+                emit({"entry": k, "lanes": lanes, "frames": frames, "layout": lname, "kernel": kernels[k], "ms": round(med, 5), "ms_min": round(min(ms[k]), 5),
+                      "ms_max": round(max(ms[k]), 5), "spread": round((max(ms[k]) - min(ms[k])) / med, 4), "bytes_per_sample": bps,
+                      "peak": round(n * bps / (med * 1e-3) / HBM_PEAK, 4), "time_over_i32": round(med / ref, 4)})
+    if out:
+        out.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
