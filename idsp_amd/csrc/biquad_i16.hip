@@ -11,13 +11,6 @@ namespace {
 
 using namespace bq16;
 
-// bytes from the first to one past the last element of `rows` rows of `row` i16 elements, `pitch` elements apart; saturating
-inline size_t extent_bytes(size_t rows, size_t row, size_t pitch)
-{
-    const size_t lead = span_bytes(rows - 1, pitch, 2), last = span_bytes(row, 1, 2);
-    return lead > SIZE_MAX - last ? SIZE_MAX : lead + last;
-}
-
 inline void pack(Sec &d, const int16_t (&ba)[5], int frac)
 {
     d.b0lo = uint16_t(ba[0]), d.b0hi = uint32_t(uint16_t(ba[0])) << 16;
@@ -75,19 +68,11 @@ int entry(const Cfg *cfg, size_t n, void *state, const int16_t *x, size_t x_pitc
     if (int rc = check_stream_args(cfg, n, state, x, y, lanes, frames, layout)) return rc;
     for (size_t k = 0; k < n; k++)  // the shift of the i32 accumulator, the rule of idsp_biquad_i32 (biquad.rs:448-450)
         if (cfg[k].frac < 0 || cfg[k].frac > 31) return fail(IDSP_EINVAL, "section %zu: frac = %d not in 0..31", k, int(cfg[k].frac));
-    const size_t row = layout == IDSP_LANE_MAJOR ? frames : lanes, rows = layout == IDSP_LANE_MAJOR ? lanes : frames;
-    if ((x_pitch && x_pitch < row) || (y_pitch && y_pitch < row))
-        return fail(IDSP_EINVAL, "pitch (%zu, %zu) shorter than a row of %zu elements", x_pitch, y_pitch, row);
+    // x and y on the 2-byte grid; y == x with one pitch is the reference's inplace() (biquad.rs:540-541)
+    subword::PitchedRows r;
+    if (int rc = subword::pitched_rows(r, layout, lanes, frames, x, x_pitch, 2, y, y_pitch, 2, subword::InPlace::same_rows)) return rc;
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    if (reinterpret_cast<uintptr_t>(x) % 2 || reinterpret_cast<uintptr_t>(y) % 2) return fail(IDSP_EINVAL, "x and y must be 2-byte aligned");
-    const size_t xl = x_pitch ? x_pitch : row, yl = y_pitch ? y_pitch : row;
-    const size_t xn = extent_bytes(rows, row, xl), yn = extent_bytes(rows, row, yl);
-    if (xn == SIZE_MAX || yn == SIZE_MAX) return fail(IDSP_EINVAL, "rows * pitch out of range");
-    if (x == y) {  // the reference's inplace() (biquad.rs:540-541)
-        if (xl != yl) return fail(IDSP_EINVAL, "in-place call with different x and y pitches (%zu, %zu)", xl, yl);
-    } else if (ranges_overlap(x, xn, y, yn)) {
-        return fail(IDSP_EINVAL, "x and y overlap without being the same rows (in place is y == x with one pitch)");
-    }
+    const size_t row = r.row, rows = r.rows, xl = r.xl, yl = r.yl;
     hipStream_t s = as_stream(stream);
     if (n == 0) {  // empty slice: y.copy_from_slice(x), compose.rs:63-65
         if (x != y) IDSP_HIP_TRY(hipMemcpy2DAsync(y, yl * 2, x, xl * 2, row * 2, rows, hipMemcpyDeviceToDevice, s));

@@ -23,14 +23,13 @@
 #pragma once
 
 #include "biquad_i16_plan.h"
-#include "common.h"
+#include "subword_rows.h"
 
 namespace idsp {
 namespace bq16 {
 
-// Depth of the rotating register window of the FRAME_MAJOR kernels (frames in flight per thread), as in dsm_kernels.h: with one wave
-// per SIMD or fewer nothing but the window hides the latency of a row.
-constexpr int kFmU = 48;
+using subword::kFmU;  // depth of the rotating register window
+static_assert(kWave == subword::kWave, "biquad_i16_plan.h (no HIP: it cannot include subword_rows.h) and the walkers agree on the wave");
 constexpr int kLmTW = 64;          // dwords per lane and tile: 256-byte runs
 constexpr int kLmTS = 2 * kLmTW;   // samples per lane and tile
 
@@ -112,9 +111,8 @@ struct Core {
 };
 
 // ---------------------------------------------------------------- FRAME_MAJOR
-// One lane per thread, one 16-bit element per frame, any alignment: a wave moves 128 contiguous bytes per frame.  The rotating register
-// window of dsm_frame_major: frame f + U is requested right before frame f is consumed.  xl / yl: elements between consecutive frames.
-// In place (y == x, yl == xl) a thread only ever overwrites elements it has already consumed.
+// One lane per thread, one 16-bit element per frame, any alignment: a wave moves 128 contiguous bytes per frame, on the rotating
+// register window (subword::window_walk, which is also what makes y == x safe).  xl / yl: elements between consecutive frames.
 // (A second form was built beside this one and measured: a thread owned the adjacent lanes 2 t and 2 t + 1 and moved one dword per
 // frame, 256 B per wave, on half as many waves.  It was never faster — 65536 lanes x 4096 frames 0.207 ms against 0.199-0.208, 16384
 // lanes 0.203 against 0.158 — and was taken out.  Loads and stores share the one 6-bit vmcnt counter, so a wave has at most 63 of them
@@ -131,46 +129,17 @@ __global__ __launch_bounds__(256) void biquad_i16_frame_major(const Params<N> pr
     p.load(st, lanes, lane);
     const uint32_t voff = uint32_t(lane) * 2u;  // the thread's bytes into a row (lanes <= 2^31); the row base is wave-uniform: SGPRs
 
-    auto ld = [&](size_t f) -> uint32_t { return global_ld<uint16_t, true>(x + f * xl, voff); };
-    auto run = [&](uint32_t v, size_t f) { global_st<uint16_t, true>(y + f * yl, voff, uint16_t(p.template step<false>(prm, v))); };
-
-    uint32_t ring[U];
-#pragma unroll
-    for (int u = 0; u < U; u++)
-        if (size_t(u) < frames) ring[u] = ld(size_t(u));
-    size_t f = 0;
-    for (; f + 2 * U <= frames; f += U) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t v = ring[u];
-            ring[u] = ld(f + U + u);
-            run(v, f + u);
-        }
-    }
-    // drain: fewer than 2 U frames left, predicates are wave-uniform
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const size_t fr = f + u;
-        if (fr < frames) {
-            const uint32_t v = ring[u];
-            if (fr + U < frames) ring[u] = ld(fr + U);
-            run(v, fr);
-        }
-    }
-    f += U;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const size_t fr = f + u;
-        if (fr < frames) run(ring[u], fr);
-    }
+    subword::window_walk<U>(
+        frames, [&](size_t f) -> uint32_t { return global_ld<uint16_t, true>(x + f * xl, voff); },
+        [&](uint32_t v, size_t f) { global_st<uint16_t, true>(y + f * yl, voff, uint16_t(p.template step<false>(prm, v))); });
     p.store(st, lanes, lane);
 }
 
 // ----------------------------------------------------------------- LANE_MAJOR
-// Adjacent lanes are a pitch apart, so a wave (one per workgroup) moves 64-lane x 128-sample tiles through one padded LDS tile of 64
-// x 64 dwords, as dsm_lane_major does: a load instruction takes 64 consecutive dwords (128 samples) of ONE lane, the next tile's 64
-// loads are in flight during the arithmetic, the owning thread walks its row conflict-free and leaves the two outputs of a dword
-// where the two inputs were, and a store instruction writes 64 dwords of one lane.
+// A wave (one per workgroup) moves 64-lane x 128-sample tiles through one padded LDS tile of 64 x 64 dwords on the front end of
+// subword_rows.h (WaveRows, fetch_dwords, deposit): a load instruction takes 64 consecutive dwords (128 samples) of ONE lane, the next
+// tile's 64 loads are in flight during the arithmetic, the owning thread walks its row conflict-free and leaves the two outputs of a
+// dword where the two inputs were, and a store instruction writes 64 dwords of one lane.
 // `grid4` (x, y on the 4-byte grid and xl, yl even): whole tiles move as dwords.  Otherwise, and in the last, partial tile of a
 // lane, every dword is put together from / taken apart into two 16-bit accesses, each predicated on its own sample: nothing outside
 // the `frames` elements of a lane is read or written.  (With `grid4` the partial tile still moves dwords wherever both samples exist.)
@@ -184,10 +153,10 @@ __global__ __launch_bounds__(kWave) void biquad_i16_lane_major(const Params<N> p
     static_assert(TW == kWave, "a load instruction covers one row of the tile");
     __shared__ uint32_t tile[kWave][TW + 1];
 
-    const int lid = threadIdx.x;
-    const size_t lane0 = size_t(blockIdx.x) * kWave, lane = lane0 + lid;
-    const bool active = lane < lanes;
-    const size_t nrows = lanes - lane0 < size_t(kWave) ? lanes - lane0 : size_t(kWave);
+    const subword::WaveRows w(lanes);
+    const int lid = w.lid;
+    const size_t lane0 = w.lane0, lane = w.lane, nrows = w.nrows;
+    const bool active = w.active;
 
     Core<N, CLAMP> p;
     if (active) p.load(st, lanes, lane);
@@ -196,10 +165,8 @@ __global__ __launch_bounds__(kWave) void biquad_i16_lane_major(const Params<N> p
     auto fetch = [&](size_t t0) {
         const size_t ns = frames - t0 < size_t(TS) ? frames - t0 : size_t(TS);
         if (grid4 && ns == size_t(TS)) {
-#pragma unroll
-            for (int r = 0; r < kWave; r++)  // wave-uniform row base in SGPRs + the thread's 32-bit offset
-                stage[r] = size_t(r) < nrows ? global_ld<uint32_t, true>(x + (lane0 + r) * xl + t0, uint32_t(lid) * 4u) : 0u;
-        } else {
+            subword::fetch_dwords(stage, w, x, xl, t0, true);  // a whole tile: no column predicate
+        } else {  // this family's own: rows off the 4-byte grid and the partial tile, a dword from two 16-bit loads
             const bool h0 = size_t(2 * lid) < ns, h1 = size_t(2 * lid + 1) < ns;
 #pragma unroll
             for (int r = 0; r < kWave; r++) {
@@ -221,8 +188,7 @@ __global__ __launch_bounds__(kWave) void biquad_i16_lane_major(const Params<N> p
     fetch(0);
     for (size_t t0 = 0; t0 < frames; t0 += TS) {
         const size_t ns = frames - t0 < size_t(TS) ? frames - t0 : size_t(TS);
-#pragma unroll
-        for (int r = 0; r < kWave; r++) tile[r][lid] = stage[r];
+        subword::deposit(tile, stage, lid);
         lds_wave_sync();
         if (t0 + TS < frames) fetch(t0 + TS);
 

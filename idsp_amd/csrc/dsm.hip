@@ -5,13 +5,6 @@
 namespace idsp {
 namespace {
 
-// bytes from the first to one past the last element of `rows` rows of `row` elements, `pitch` elements apart; saturating
-inline size_t extent_bytes(size_t rows, size_t row, size_t pitch, size_t elem)
-{
-    const size_t lead = span_bytes(rows - 1, pitch, elem), last = span_bytes(row, 1, elem);
-    return lead > SIZE_MAX - last ? SIZE_MAX : lead + last;
-}
-
 template <int K>
 int launch_dsm(uint32_t *st, const uint32_t *x, size_t xl, int8_t *y, size_t yl, size_t lanes, size_t frames, int layout, hipStream_t s)
 {
@@ -47,15 +40,10 @@ int idsp_dsm_u32(int order, void *state, const uint32_t *x, size_t x_pitch, int8
     if (!x || !y) return fail(IDSP_EINVAL, "x or y is NULL");
     if (order > 0 && !state) return fail(IDSP_EINVAL, "state is NULL");
     if (lanes > (size_t(1) << 31) || frames > (size_t(1) << 40)) return fail(IDSP_EINVAL, "lanes/frames out of range");
-    const size_t row = layout == IDSP_LANE_MAJOR ? frames : lanes, rows = layout == IDSP_LANE_MAJOR ? lanes : frames;
-    if ((x_pitch && x_pitch < row) || (y_pitch && y_pitch < row))
-        return fail(IDSP_EINVAL, "pitch (%zu, %zu) shorter than a row of %zu elements", x_pitch, y_pitch, row);
+    subword::PitchedRows r;  // x on its 4-byte grid, any y, no overlap
+    if (int rc = subword::pitched_rows(r, layout, lanes, frames, x, x_pitch, 4, y, y_pitch, 1, subword::InPlace::never)) return rc;
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    if (reinterpret_cast<uintptr_t>(x) % 4) return fail(IDSP_EINVAL, "x must be 4-byte aligned");
-    const size_t xl = x_pitch ? x_pitch : row, yl = y_pitch ? y_pitch : row;
-    const size_t xn = extent_bytes(rows, row, xl, 4), yn = extent_bytes(rows, row, yl, 1);
-    if (xn == SIZE_MAX || yn == SIZE_MAX) return fail(IDSP_EINVAL, "rows * pitch out of range");
-    if (ranges_overlap(x, xn, y, yn)) return fail(IDSP_EINVAL, "x and y overlap (there is no in-place form: the elements differ in size)");
+    const size_t xl = r.xl, yl = r.yl;
     uint32_t *st = static_cast<uint32_t *>(state);
     hipStream_t s = as_stream(stream);
     switch (order) {

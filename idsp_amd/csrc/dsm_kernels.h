@@ -1,7 +1,7 @@
 // dsm_kernels.h — the MASH-(1)^K delta-sigma modulator of the reference (`Dsm<K>`, src/dsm.rs:44-57) per lane: u32 samples in,
 // one i8 per sample out.  The first kernels of the library whose output element is smaller than a 32-bit word (lane_stream.h asserts
-// "samples are one or two 32-bit words" in every kernel), so they move their own bytes; the arithmetic is a few dozen full-rate VALU
-// operations per sample against 5 bytes, and how the bytes leave is what the two kernels are about.
+// "samples are one or two 32-bit words" in every kernel), so they move their own bytes, on the walkers of subword_rows.h; the arithmetic
+// is a few dozen full-rate VALU operations per sample against 5 bytes, and how the bytes leave is what the two kernels are about.
 //
 // Semantics, as a RELEASE build of the reference computes them (every u32 and i8 operation wraps):
 //   * stage fold (:47-51): a[i], carry[i] = a[i].overflowing_add(v), v = x for stage 0 and the new a[i - 1] after it;
@@ -17,19 +17,14 @@
 // back sign-extended.
 #pragma once
 
-#include "common.h"
+#include "subword_rows.h"
 
 namespace idsp {
 namespace dsm {
 
-constexpr int kWave = 64;
+using subword::kFmU;  // depth of the rotating register window: measured on these kernels (subword_rows.h)
+using subword::kWave;
 constexpr int kFmBlock = 256;  // four waves, 256 lanes of a row: 1 KiB in, 256 bytes out per frame
-// Depth of the rotating register window (frames in flight per thread).  Measured at 4096 frames, ms per call with 16 / 32 / 48
-// (profiles/NOTES.md, "Dsm"): 65536 lanes K = 1 0.265 / 0.268 / 0.265, K = 3 0.289 / 0.248 / 0.267, K = 8 0.369 / 0.310 / 0.288; 16384
-// lanes K = 1 0.222 / 0.180 / 0.161, K = 3 0.255 / 0.198 / 0.149, K = 8 0.345 / 0.293 / 0.261.  At one wave per SIMD or fewer nothing
-// but the window hides the latency of a row.  With 48 the K = 8 kernel holds 151 VGPRs: three waves per SIMD; lane counts that
-// would fill more (above 196608) have not been measured.
-constexpr int kFmU = 48;
 constexpr int kLmTS = 64;  // samples per lane and input tile: 256-byte runs in
 // Input tiles per output tile: outputs leave as runs of 64 kLmOT bytes per lane.  Measured with 1 / 2 / 4 at 65536 lanes x 4096 frames:
 // K = 1 0.419 / 0.350 / 0.377 ms, K = 3 0.429 / 0.409 / 0.398, K = 8 0.520 / 0.503 / 0.506; at 16384 lanes the three are within 1 %
@@ -99,9 +94,9 @@ struct Core {
 };
 
 // ---------------------------------------------------------------- FRAME_MAJOR
-// One lane per thread, the rotating register window of stream_frame_major (lane_stream.h): frame f + U is requested right before
-// frame f is consumed.  xl / yl: elements between consecutive frames of x / y.  One byte store per thread and frame: a wave writes
-// 64 contiguous bytes, whatever the alignment of y.
+// One lane per thread on a rotating register window (frame f + U is requested right before frame f is consumed): one word load and one
+// byte store per thread and frame, so a wave writes 64 contiguous bytes, whatever the alignment of y.  xl / yl: elements between
+// consecutive frames of x / y.
 // (A second store form was built beside this one and measured: a thread kept the bytes of four frames, the four threads of a quad
 // transposed their 4 x 4 bytes with two quad_perm DPP moves and each stored one dword.  It took 1.10 to 1.23 times this form's time
 // at 65536 and 16384 lanes x 4096 frames, K = 1, 3, 8 — profiles/NOTES.md, "Dsm" — and was taken out.)
@@ -117,6 +112,8 @@ __global__ __launch_bounds__(kFmBlock) void dsm_frame_major(uint32_t *st, const 
     const uint32_t *xp = x + lane;
     int8_t *yp = y + lane;
 
+    // The window of subword::window_walk, written out: on the shared walker this kernel measured slower at 65536 lanes x 4096 frames in
+    // both runs of an A/B against this form (K = 1 + 2.6 %, K = 3 and 8 + 0.3 %; profiles/NOTES.md, "Sub-word rows").
     uint32_t ring[U];
 #pragma unroll
     for (int u = 0; u < U; u++)
@@ -152,10 +149,11 @@ __global__ __launch_bounds__(kFmBlock) void dsm_frame_major(uint32_t *st, const 
 }
 
 // ----------------------------------------------------------------- LANE_MAJOR
-// Adjacent lanes are a pitch apart, so a wave (one per workgroup) moves 64-lane x 64-sample tiles through a padded LDS tile, as
-// stream_lane_major does: a load instruction takes 64 consecutive words of ONE lane (the next tile's 64 loads are in flight during the
+// A wave (one per workgroup) moves 64-lane x 64-sample tiles through a padded LDS tile on the front end of subword_rows.h (WaveRows,
+// fetch_dwords, deposit): a load instruction takes 64 consecutive words of ONE lane (the next tile's 64 loads are in flight during the
 // arithmetic), the owning thread walks its row conflict-free, packs four output bytes to a word and leaves 16 words per lane and
-// input tile in the output tile.  The output tile collects OT input tiles, so outputs leave as runs of 64 OT bytes per lane: as
+// input tile in the output tile.  The second, output tile is this family's own: it collects OT input tiles, so outputs leave as runs
+// of 64 OT bytes per lane: as
 // dwords where the runs are 4-byte aligned (`aligned`: y and yl multiples of 4; a run starts at a multiple of 64 samples), byte by
 // byte otherwise (unaligned rows) and for the last frames % 4 bytes of a lane.
 // xl / yl: elements between the starts of consecutive lanes of x / y.
@@ -169,10 +167,10 @@ __global__ __launch_bounds__(kWave) void dsm_lane_major(uint32_t *st, const uint
     __shared__ uint32_t tin[kWave][TS + 1];
     __shared__ uint32_t tout[kWave][OWR + 1];
 
-    const int lid = threadIdx.x;
-    const size_t lane0 = size_t(blockIdx.x) * kWave, lane = lane0 + lid;
-    const bool active = lane < lanes;
-    const size_t nrows = lanes - lane0 < size_t(kWave) ? lanes - lane0 : size_t(kWave);
+    const subword::WaveRows w(lanes);
+    const int lid = w.lid;
+    const size_t lane0 = w.lane0, lane = w.lane, nrows = w.nrows;
+    const bool active = w.active;
 
     Core<K> p;
     if (active) p.load(st, lanes, lane);
@@ -180,9 +178,7 @@ __global__ __launch_bounds__(kWave) void dsm_lane_major(uint32_t *st, const uint
     uint32_t stage[kWave];
     auto fetch = [&](size_t t0) {
         const size_t nw = frames - t0 < size_t(TS) ? frames - t0 : size_t(TS);
-#pragma unroll
-        for (int r = 0; r < kWave; r++)  // wave-uniform row base in SGPRs + the thread's 32-bit offset: no 64-bit address per row in VGPRs
-            stage[r] = (size_t(r) < nrows && size_t(lid) < nw) ? global_ld<uint32_t, true>(x + (lane0 + r) * xl + t0, uint32_t(lid) * 4u) : 0u;
+        subword::fetch_dwords(stage, w, x, xl, t0, size_t(lid) < nw);
     };
 
     fetch(0);
@@ -190,8 +186,7 @@ __global__ __launch_bounds__(kWave) void dsm_lane_major(uint32_t *st, const uint
     for (size_t t0 = 0; t0 < frames; t0 += TS, tile++) {
         const size_t ncols = frames - t0 < size_t(TS) ? frames - t0 : size_t(TS);
         const int part = int(tile % OT);  // which part of the output tile this input tile fills
-#pragma unroll
-        for (int r = 0; r < kWave; r++) tin[r][lid] = stage[r];
+        subword::deposit(tin, stage, lid);
         lds_wave_sync();
         if (t0 + TS < frames) fetch(t0 + TS);
 

@@ -250,6 +250,7 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major(
         // times (vmcnt is in-order: the wait for frame f tolerates the U-1
         // younger loads and the interleaved stores).  Reads always run ahead of
         // this thread's writes, so y == x is safe.
+        // (The sub-word families share this walk as subword_rows.h: window_walk; this one keeps its own for BATCH / `pre`.)
         In ring[U];
 #pragma unroll
         for (int u = 0; u < U; u++)

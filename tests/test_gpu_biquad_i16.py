@@ -10,15 +10,16 @@ import torch
 
 from idsp_amd import _abi
 from tests import _biquad_i16_spec as S
+from tests import _subword_rows as R
 from tests._guard import Guards
+from tests._subword_rows import DEV, FM, LM, POISON
+from tests._subword_rows import rows_of as _rows
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-FM, LM = _abi.FRAME_MAJOR, _abi.LANE_MAJOR
-POISON = -77
 XGAP = 0x5A5A  # what the gaps of a pitched x hold
 FRAMES = "biquad_i16_frame_major"
 DWORDS, HALVES = "biquad_i16_lane_major[dword runs]", "biquad_i16_lane_major[half runs]"
+K = {**R.constants("subword_rows.h"), **R.constants("biquad_i16_kernels.h")}  # kFmU, kLmTW, kLmTS
 
 SHAPES = [(1, 1), (1, 1000), (2, 3), (3, 5), (5, 9), (63, 33), (64, 32), (65, 31), (127, 7), (128, 8), (129, 2), (255, 257), (256, 8), (257, 1),
           (511, 3), (512, 4), (513, 5), (1000, 1000), (4099, 33), (16384, 130), (24577, 33), (65537, 33)]
@@ -26,21 +27,7 @@ NS = [1, 2, 4, 5, 9]
 
 
 def _ptr(t, off_elems=0):
-    return C.c_void_p(t.data_ptr() + 2 * off_elems) if t is not None else None
-
-
-def _rows(layout, lanes, frames):
-    """(rows, row): FrameMajor rows are frames of `lanes` elements, LaneMajor rows are lanes of `frames` elements"""
-    return (frames, lanes) if layout == FM else (lanes, frames)
-
-
-def _pitched(a2d, pitch, gap):
-    """[rows, row] -> flat buffer of (rows - 1) * pitch + row elements, `gap` between the rows"""
-    rows, row = a2d.shape
-    buf = np.full((rows - 1) * pitch + row, gap, a2d.dtype)
-    for r in range(rows):
-        buf[r * pitch:r * pitch + row] = a2d[r]
-    return buf
+    return R.ptr(t, 2 * off_elems)
 
 
 def cfg_of(secs):
@@ -66,36 +53,19 @@ def kernel_for(layout, lanes, x_addr, y_addr, xl, yl):
 def run(gpu, secs, layout, st, x, xp=0, yp=0, x_off=0, y_off=0, inplace=False, clamped=False):
     """one call; x: [frames, lanes] int16, st: [4 n, lanes] uint32 -> (y [frames, lanes] int16, state after, kernel name).  x_off / y_off:
     ELEMENTS between the 512-byte grid and the first sample.  Checks the guard bands, the read-only x, the gaps of y and the kernel."""
-    frames, lanes = x.shape
-    rows, row = _rows(layout, lanes, frames)
-    if inplace:
-        yp, y_off = xp, x_off
-    xl, yl = xp or row, yp or row
-    g = Guards(DEV)
-    x2 = x if layout == FM else np.ascontiguousarray(x.T)
-    xd = g.upload("x", _pitched(x2, xl, np.int16(XGAP)), off=2 * x_off, readonly=not inplace)
-    yd = xd if inplace else g.full("y", (rows - 1) * yl + row, torch.int16, POISON, off=2 * y_off)
-    sd = g.upload("state", st)
     name, cfg = cfg_of(secs)
     if not secs and clamped:
         name = "biquad_i16_df1_clamp"
-    rc = gpu.fn[name](cfg, len(secs), _ptr(sd), _ptr(xd), xp, _ptr(yd), yp, lanes, frames, layout, None)
-    torch.cuda.synchronize()
-    kernel = gpu.last_kernel()
-    what = (name, len(secs), layout, lanes, frames, xp, yp, x_off, y_off, inplace, kernel)
-    assert rc == 0, (what, gpu.err())
-    g.check(what)
-    if secs:  # the last pass of a chain longer than one launch runs in place on y
-        last_x, last_xl = (xd, xl) if len(secs) <= 4 else (yd, yl)
-        assert kernel == kernel_for(layout, lanes, last_x.data_ptr(), yd.data_ptr(), last_xl, yl), what
-    yb = yd.cpu().numpy()
-    idx = (np.arange(rows)[:, None] * yl + np.arange(row)[None, :]).reshape(-1)
-    gap = np.ones(yb.size, bool)
-    gap[idx] = False
-    assert (yb[gap] == (np.int16(XGAP) if inplace else POISON)).all(), ("a gap element of y was written", what)
-    y2 = yb[idx].reshape(rows, row)
-    y = y2 if layout == FM else np.ascontiguousarray(y2.T)
-    return y, sd.cpu().numpy().view(np.uint32).reshape(st.shape), kernel
+
+    def kernel_ok(kernel, x_addr, y_addr, xl, yl):
+        if not secs:
+            return True
+        if len(secs) > 4:  # the last pass of a chain longer than one launch runs in place on y
+            x_addr, xl = y_addr, yl
+        return kernel == kernel_for(layout, x.shape[1], x_addr, y_addr, xl, yl)
+
+    return R.run(gpu, lambda *a: gpu.fn[name](cfg, len(secs), *a, None), layout, st, x, x_gap=np.int16(XGAP), y_dtype=torch.int16, kernel_ok=kernel_ok,
+                 xp=xp, yp=yp, x_off=2 * x_off, y_off=2 * y_off, inplace=inplace, what=(name, len(secs)))
 
 
 def _case(n, clamped, lanes, frames, seed, zero_state=False):
@@ -135,10 +105,6 @@ def test_every_kernel_form(gpu, layout, lanes, frames, xp, x_off, kernel):
     assert np.array_equal(y, want) and np.array_equal(got_st, want_st)
 
 
-def _pitches(row):
-    return [0, row + 1, row + 3, -(-row // 2) * 2, -(-row // 32) * 32]
-
-
 @pytest.mark.parametrize("layout", [FM, LM])
 @pytest.mark.parametrize("n,clamped", [(1, False), (2, True), (5, False)])
 def test_alignment_and_pitch(gpu, n, clamped, layout):
@@ -147,12 +113,8 @@ def test_alignment_and_pitch(gpu, n, clamped, layout):
     dense aligned partner, then both walk together"""
     for i, (lanes, frames) in enumerate([(5, 9), (65, 31), (130, 129)]):
         secs, x, st, want, want_st = _case(n, clamped, lanes, frames, 50 * n + i)
-        row = _rows(layout, lanes, frames)[1]
-        ps = _pitches(row)
-        combos = [(0, 0, y_off, yp) for y_off in range(8) for yp in ps]
-        combos += [(x_off, xp, 0, 0) for x_off in range(8) for xp in ps]
-        combos += [(i % 8, ps[(i + 1) % 5], (3 * i + 1) % 8, ps[(2 * i + 3) % 5]) for i in range(10)]
-        for x_off, xp, y_off, yp in combos:
+        ps = R.pitches(_rows(layout, lanes, frames)[1], 2, 32)
+        for x_off, xp, y_off, yp in R.combos(ps, x_offs=range(8), y_offs=range(8), both=10, y_step=3):
             y, got_st, kernel = run(gpu, secs, layout, st, x, xp=xp, yp=yp, x_off=x_off, y_off=y_off)
             what = (n, clamped, layout, lanes, frames, x_off, xp, y_off, yp, kernel)
             assert np.array_equal(y, want), what
@@ -167,7 +129,7 @@ def test_inplace(gpu, n, clamped, layout):
         secs, x, st, want, want_st = _case(n, clamped, lanes, frames, 70 * n + i)
         row = _rows(layout, lanes, frames)[1]
         for off in (0, 1, 2):
-            for xp in _pitches(row):
+            for xp in R.pitches(row, 2, 32):
                 y, got_st, kernel = run(gpu, secs, layout, st, x, xp=xp, x_off=off, inplace=True)
                 what = (n, clamped, layout, lanes, frames, off, xp, kernel)
                 assert np.array_equal(y, want), what
@@ -204,6 +166,32 @@ def test_chunks(gpu, n, clamped, lanes, frames, chunks):
         assert np.array_equal(cur, want_st), (n, lanes, frames, layouts, "state")
     one, one_st, _ = run(gpu, secs, LM, st, x)
     assert np.array_equal(one, want) and np.array_equal(one_st, want_st)
+
+
+@pytest.mark.parametrize("layout", [FM, LM])
+@pytest.mark.parametrize("n,clamped", [(1, False), (1, True), (4, False), (4, True)])
+def test_window_and_tile_edges(gpu, n, clamped, layout):
+    """frame counts one below, at and one above the counts the walkers of idsp_amd/csrc/subword_rows.h turn on — FrameMajor the window
+    depth U, 2 U and 3 U + 1, out of place and in place; LaneMajor the tile TS and 2 TS, with rows on the dword grid (an even pitch), off
+    it (x one element further) and in place — in 3 lanes and in 65 (two waves, the last one ragged): one call, and two calls cut at U / TS
+    on one state, equal the spec in every element and every state word"""
+    U, TS = K["kFmU"], K["kLmTS"]
+    counts, cut = (R.around(U, 2 * U) + [3 * U + 1], U) if layout == FM else (R.around(TS, 2 * TS), TS)
+    # (x_off, inplace, kernel)
+    forms = [(0, False, FRAMES), (0, True, FRAMES)] if layout == FM else [(0, False, DWORDS), (1, False, HALVES), (0, True, DWORDS)]
+    for lanes in (3, 65):
+        for i, frames in enumerate(counts):
+            secs, x, st, want, want_st = _case(n, clamped, lanes, frames, 300 * n + 100 * clamped + 10 * lanes + i)
+            pitch = 0 if layout == FM else -(-frames // 2) * 2
+            for x_off, inplace, kernel in forms:
+                def one(s, xs):
+                    y, got_st, got = run(gpu, secs, layout, s, xs, xp=pitch, yp=pitch, x_off=x_off, inplace=inplace)
+                    assert got == kernel, (n, clamped, layout, lanes, frames, x_off, inplace)
+                    return y, got_st
+
+                for y, got_st in R.whole_and_split(one, st, x, cut):
+                    assert np.array_equal(y, want), (n, clamped, layout, lanes, frames, x_off, inplace)
+                    assert np.array_equal(got_st, want_st), (n, clamped, layout, lanes, frames, x_off, inplace, "state")
 
 
 @pytest.mark.parametrize("layout", [FM, LM])

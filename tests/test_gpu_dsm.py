@@ -1,70 +1,33 @@
 """idsp_dsm_u32 on the device against tests/_dsm_spec.py: every output byte and every state word, `array_equal`.  Outputs start
 poisoned with -77, every buffer sits in the guard bands of tests/_guard.py, x is uploaded read-only, and the gap bytes of a pitched
 y row must keep their poison."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from idsp_amd import _abi
 from tests import _dsm_spec as S
+from tests import _subword_rows as R
 from tests._guard import Guards
+from tests._subword_rows import DEV, FM, LM, POISON
+from tests._subword_rows import ptr as _ptr
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-FM, LM = _abi.FRAME_MAJOR, _abi.LANE_MAJOR
-POISON = -77
 XGAP = 0x5A5A5A5A  # what the gaps of a pitched x hold
 PREFIX = {FM: "dsm_frame_major", LM: "dsm_lane_major"}
+K = {**R.constants("subword_rows.h"), **R.constants("dsm_kernels.h")}  # kFmU, kLmTS, kLmOT
 
 SHAPES = [(1, 1), (1, 1000), (2, 3), (3, 5), (4, 4), (5, 9), (63, 33), (64, 32), (65, 31), (127, 7), (129, 2), (255, 257), (256, 8), (257, 1),
           (1000, 1000), (4099, 33), (16384, 130), (65537, 33)]
 
 
-def _ptr(t, off_bytes=0):
-    return C.c_void_p(t.data_ptr() + off_bytes) if t is not None else None
-
-
-def _rows(layout, lanes, frames):
-    """(rows, row): FrameMajor rows are frames of `lanes` elements, LaneMajor rows are lanes of `frames` elements"""
-    return (frames, lanes) if layout == FM else (lanes, frames)
-
-
-def _pitched(a2d, pitch, gap):
-    """[rows, row] -> flat buffer of (rows - 1) * pitch + row elements, `gap` between the rows"""
-    rows, row = a2d.shape
-    buf = np.full((rows - 1) * pitch + row, gap, a2d.dtype)
-    for r in range(rows):
-        buf[r * pitch:r * pitch + row] = a2d[r]
-    return buf
-
-
-def run(gpu, order, layout, st, x, xp=0, yp=0, x_off=0, y_off=0, null_state=False):
-    """one call; x: [frames, lanes] uint32, st: [2 K, lanes] uint32 -> (y [frames, lanes] int8, state after).  Checks the guard
-    bands, the read-only x, the gaps of y and the kernel name."""
-    frames, lanes = x.shape
-    rows, row = _rows(layout, lanes, frames)
-    xl, yl = xp or row, yp or row
-    g = Guards(DEV)
-    x2 = x if layout == FM else np.ascontiguousarray(x.T)
-    xd = g.upload("x", _pitched(x2, xl, np.uint32(XGAP)), off=x_off, readonly=True)
-    yd = g.full("y", (rows - 1) * yl + row, torch.int8, POISON, off=y_off)
-    sd = None if null_state else g.upload("state", st)
-    rc = gpu.fn["dsm_u32"](order, _ptr(sd), _ptr(xd), xp, _ptr(yd), yp, lanes, frames, layout, None)
-    torch.cuda.synchronize()
-    what = (order, layout, lanes, frames, xp, yp, x_off, y_off, gpu.last_kernel())
-    assert rc == 0, (what, gpu.err())
-    g.check(what)
-    assert gpu.last_kernel().startswith(PREFIX[layout]), what
-    yb = yd.cpu().numpy()
-    idx = (np.arange(rows)[:, None] * yl + np.arange(row)[None, :]).reshape(-1)
-    gap = np.ones(yb.size, bool)
-    gap[idx] = False
-    assert (yb[gap] == POISON).all(), ("a gap byte of y was written", what)
-    y2 = yb[idx].reshape(rows, row)
-    y = y2 if layout == FM else np.ascontiguousarray(y2.T)
-    return y, (st.copy() if null_state else sd.cpu().numpy().view(np.uint32).reshape(st.shape))
+def run(gpu, order, layout, st, x, xp=0, yp=0, x_off=0, y_off=0, null_state=False, kernel=None):
+    """one call; x: [frames, lanes] uint32, st: [2 K, lanes] uint32 -> (y [frames, lanes] int8, state after).  x_off / y_off: bytes.
+    Checks the guard bands, the read-only x, the gaps of y and the kernel name (its prefix, or all of it where `kernel` is given)."""
+    y, got_st, _ = R.run(gpu, lambda *a: gpu.fn["dsm_u32"](order, *a, None), layout, st, x, x_gap=np.uint32(XGAP), y_dtype=torch.int8,
+                         kernel_ok=lambda k, *_: k == kernel if kernel else k.startswith(PREFIX[layout]), xp=xp, yp=yp, x_off=x_off, y_off=y_off,
+                         null_state=null_state, what=("dsm_u32", order))
+    return y, got_st
 
 
 def _case(order, lanes, frames, seed, zero_state=False):
@@ -93,10 +56,6 @@ def test_parity(gpu, order):
             assert not y.any()
 
 
-def _pitches(row):
-    return [0, row + 1, row + 3, -(-row // 4) * 4, -(-row // 64) * 64]
-
-
 @pytest.mark.parametrize("layout", [FM, LM])
 @pytest.mark.parametrize("order", [1, 3, 8])
 def test_alignment_and_pitch(gpu, order, layout):
@@ -104,11 +63,8 @@ def test_alignment_and_pitch(gpu, order, layout):
     side and the x side each walk all their (offset, pitch) pairs against a dense aligned partner, then both walk together"""
     for n, (lanes, frames) in enumerate([(5, 9), (65, 31), (1000, 33)]):
         x, st, want, want_st = _case(order, lanes, frames, 50 * order + n)
-        row = _rows(layout, lanes, frames)[1]
-        ps = _pitches(row)
-        combos = [(0, 0, y_off, yp) for y_off in range(4) for yp in ps]
-        combos += [(x_off, xp, 0, 0) for x_off in (0, 4, 8, 12) for xp in ps]
-        combos += [(4 * (i % 4), ps[(i + 1) % 5], (i + 1) % 4, ps[(2 * i + 3) % 5]) for i in range(5)]
+        ps = R.pitches(R.rows_of(layout, lanes, frames)[1], 4, 64)
+        combos = R.combos(ps, x_offs=(0, 4, 8, 12), y_offs=range(4), both=5, y_step=1)
         for x_off, xp, y_off, yp in combos:
             y, got_st = run(gpu, order, layout, st, x, xp=xp, yp=yp, x_off=x_off, y_off=y_off)
             what = (order, layout, lanes, frames, x_off, xp, y_off, yp, gpu.last_kernel())
@@ -132,6 +88,27 @@ def test_chunks(gpu, order, lanes, frames, chunks):
         assert np.array_equal(cur, want_st), (order, lanes, frames, layouts, "state")
     one, one_st = run(gpu, order, LM, st, x)
     assert np.array_equal(one, want) and np.array_equal(one_st, want_st)
+
+
+@pytest.mark.parametrize("layout", [FM, LM])
+@pytest.mark.parametrize("order", [1, 8])
+def test_window_and_tile_edges(gpu, order, layout):
+    """frame counts one below, at and one above the counts the walkers of idsp_amd/csrc/subword_rows.h turn on — FrameMajor the window
+    depth U, 2 U and 3 U + 1; LaneMajor the input tile TS, the output tile OT TS and one past the next input tile, each on an aligned y
+    with a pitch of whole dwords (dword runs) and on the same rows one byte further (byte runs) — in 3 lanes and in 65 (two waves, the last
+    one ragged): one call, and two calls cut at U / TS on one state, equal the spec in every byte and every state word"""
+    U, TS, OT = K["kFmU"], K["kLmTS"], K["kLmOT"]
+    counts, cut = (R.around(U, 2 * U) + [3 * U + 1], U) if layout == FM else (R.around(TS, OT * TS) + [(OT + 1) * TS + 1], TS)
+    forms = [(0, None)] if layout == FM else [(0, "dsm_lane_major[dword runs]"), (1, "dsm_lane_major[byte runs]")]
+    for lanes in (3, 65):
+        for n, frames in enumerate(counts):
+            x, st, want, want_st = _case(order, lanes, frames, 300 * order + 10 * lanes + n)
+            yp = 0 if layout == FM else -(-frames // 4) * 4
+            for y_off, kernel in forms:
+                one = lambda s, xs: run(gpu, order, layout, s, xs, yp=yp, y_off=y_off, kernel=kernel)  # noqa: E731
+                for y, got_st in R.whole_and_split(one, st, x, cut):
+                    assert np.array_equal(y, want), (order, layout, lanes, frames, y_off)
+                    assert np.array_equal(got_st, want_st), (order, layout, lanes, frames, y_off, "state")
 
 
 def test_zero_state_is_the_default_and_the_reference_doctest(gpu):

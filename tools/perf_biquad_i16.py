@@ -15,12 +15,13 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import os
 import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tools import _perf_common as PC  # noqa: E402
 
 WARMUP, CALLS, ROUNDS = 5, 100, 7
 HBM_PEAK = 8.0e12  # bytes / s
@@ -45,30 +46,12 @@ def main() -> int:
         return 2
     fn, _ = load()
     dev = "cuda:0"
-    out = open(args.out, "a") if args.out else None
+    emit = PC.line_writer(args.out, "a", args.label)
 
-    def emit(rec):
-        rec = dict(label=args.label, **rec)
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if out:
-            out.write(line + "\n")
-            out.flush()
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr())
+    ptr = PC.ptr
 
     def timed(call):
-        for _ in range(WARMUP):
-            assert call() == 0, fn["last_error"]()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(CALLS):
-            call()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / CALLS
+        return PC.timed(call, WARMUP, CALLS, fn["last_error"])
 
     ns = args.sections
     lp = (C.c_double * 6)(0.06745527388907189, 0.13491054777814377, 0.06745527388907189, 1.0, -1.1429805025399011, 0.4128015980961886)  # low-pass, f0 = 0.1
@@ -103,8 +86,6 @@ def main() -> int:
                 emit({"entry": k, "lanes": lanes, "frames": frames, "layout": lname, "kernel": kernels[k], "ms": round(med, 5), "ms_min": round(min(ms[k]), 5),
                       "ms_max": round(max(ms[k]), 5), "spread": round((max(ms[k]) - min(ms[k])) / med, 4), "bytes_per_sample": bps,
                       "peak": round(n * bps / (med * 1e-3) / HBM_PEAK, 4), "time_over_i32": round(med / ref, 4)})
-    if out:
-        out.close()
     return 0
 
 

@@ -1,24 +1,26 @@
 #!/usr/bin/env python3
 """Time idsp_dsm_u32 on an MI355X (a plain tool, not a test; profiles/NOTES.md, "Dsm").
 
-  python tools/perf_dsm.py [--out FILE.jsonl] [--lanes 65536 16384] [--frames 4096] [--orders 1 3 8]
+  python tools/perf_dsm.py [--out FILE.jsonl] [--lanes 65536 16384] [--frames 4096] [--orders 1 3 8] [--label TEXT]
 
 Per shape (65536 and 16384 lanes x 4096 frames), order K in {1, 3, 8} and layout: HIP-event time of 20 calls after 5 warm-ups, three
 rounds, the median reported with the minimum and maximum.  LaneMajor is timed twice, ALTERNATED round by round: on an aligned y (dword
 runs) and on the same buffer one byte further (byte runs) — the two store forms of the LaneMajor kernel; FrameMajor has one form (the
 packed quad store that was built beside it is in NOTES with its figures).  The comparator is idsp_unwrap_i32 at the same shape in the
 same run: 4 bytes in and 4 out per sample, trivial arithmetic, the existing launch path; Dsm moves 5 bytes per sample, 5/8 of it.
-One JSON line per measurement; needs a GPU (no fallback)."""
+One JSON line per measurement; with --label every line carries the label and --out is appended to, so that the runs of an A/B comparison
+share one file.  Needs a GPU (no fallback)."""
 from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import os
 import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tools import _perf_common as PC  # noqa: E402
 
 WARMUP, CALLS, ROUNDS = 5, 20, 3
 
@@ -29,6 +31,7 @@ def main() -> int:
     ap.add_argument("--lanes", type=int, nargs="+", default=[65536, 16384])
     ap.add_argument("--frames", type=int, default=4096)
     ap.add_argument("--orders", type=int, nargs="+", default=[1, 3, 8])
+    ap.add_argument("--label")
     args = ap.parse_args()
 
     import torch
@@ -41,29 +44,12 @@ def main() -> int:
         return 2
     fn, _ = load()
     dev = "cuda:0"
-    out = open(args.out, "w") if args.out else None
+    emit = PC.line_writer(args.out, "a" if args.label is not None else "w", args.label)
 
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if out:
-            out.write(line + "\n")
-            out.flush()
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr())
+    ptr = PC.ptr
 
     def timed(call):
-        for _ in range(WARMUP):
-            assert call() == 0, fn["last_error"]()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(CALLS):
-            call()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / CALLS
+        return PC.timed(call, WARMUP, CALLS, fn["last_error"])
 
     emit({"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "calls": CALLS, "rounds": ROUNDS, "frames": args.frames})
     for lanes in args.lanes:
@@ -92,8 +78,6 @@ def main() -> int:
                     emit({"entry": "dsm_u32", "order": order, "lanes": lanes, "frames": frames, "layout": lname, "y_offset": off, "kernel": kernels[off],
                           "ms": med, "ms_min": min(ms[off]), "ms_max": max(ms[off]), "bytes_per_sample": 5, "gbs": n * 5 / med / 1e6,
                           "time_over_unwrap": med / ref_ms})
-    if out:
-        out.close()
     return 0
 
 
