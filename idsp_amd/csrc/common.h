@@ -184,12 +184,8 @@ __device__ __forceinline__ T *uniform_ptr(T *q)
 template <class V, bool NT>
 __device__ __forceinline__ V global_ld(const void *ubase, uint32_t voff)
 {
-#ifdef IDSP_EXP_FLAT  // A/B: the generic pointer of rounds 2-5 (flat_load)
-    const auto *q = reinterpret_cast<const V *>(uniform_ptr(static_cast<const char *>(ubase)) + size_t(voff));
-#else
     const auto *g = reinterpret_cast<const __attribute__((address_space(1))) char *>(reinterpret_cast<uintptr_t>(uniform_ptr(static_cast<const char *>(ubase))));
     const auto *q = reinterpret_cast<const __attribute__((address_space(1))) V *>(g + voff);
-#endif
     if constexpr (NT)
         return __builtin_nontemporal_load(q);
     else
@@ -198,12 +194,8 @@ __device__ __forceinline__ V global_ld(const void *ubase, uint32_t voff)
 template <class V, bool NT>
 __device__ __forceinline__ void global_st(void *ubase, uint32_t voff, V v)
 {
-#ifdef IDSP_EXP_FLAT
-    auto *q = reinterpret_cast<V *>(uniform_ptr(static_cast<char *>(ubase)) + size_t(voff));
-#else
     auto *g = reinterpret_cast<__attribute__((address_space(1))) char *>(reinterpret_cast<uintptr_t>(uniform_ptr(static_cast<char *>(ubase))));
     auto *q = reinterpret_cast<__attribute__((address_space(1))) V *>(g + voff);
-#endif
     if constexpr (NT)
         __builtin_nontemporal_store(v, q);
     else

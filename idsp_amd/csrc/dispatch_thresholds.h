@@ -53,8 +53,6 @@ constexpr size_t kRoundsSplitMinFrames = 16, kRoundsSplitMaxRounds = 16;
 constexpr size_t kStagedMinFrames = 16, kStagedXcdcMinGrid = 64;
 // sweep kernel: XCD-contiguous block order from this many workgroups; several frames per segment up to this many lanes per block
 constexpr size_t kSweepXcdcMinGrid = 8, kSweepFpsMaxBlockLanes = 128;
-// round-3 LDS-DMA kernel: several lanes per thread only when that leaves this many workgroups
-constexpr size_t kLdsLptMinGrid = 224, kLdsLptMaxGrid = 320;
 // register-window kernel: 256-thread workgroups from this many waves (below: one wave per workgroup, to reach all 256 CUs), the deep
 // prefetch window up to this many waves, XCD-contiguous blocks (a diagnostic switch) from this many workgroups
 constexpr size_t kWindowBlockMinWaves = 1024, kWindowDeepMaxWaves = 2048, kWindowXcdcMinGrid = 64;

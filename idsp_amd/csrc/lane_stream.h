@@ -165,12 +165,6 @@ struct WordsOf<16> {
 template <bool NT, class T>
 __device__ __forceinline__ T nt_load(const T *p)
 {
-#ifdef IDSP_EXP_GENERIC_NT  // A/B: the generic-pointer form of rounds 1-5
-    if constexpr (NT)
-        return __builtin_nontemporal_load(p);
-    else
-        return *p;
-#endif
     using W = typename WordsOf<int(sizeof(T))>::type;
     const auto *g = reinterpret_cast<const __attribute__((address_space(1))) W *>(reinterpret_cast<uintptr_t>(p));
     if constexpr (NT)
@@ -181,17 +175,6 @@ __device__ __forceinline__ T nt_load(const T *p)
 template <bool NT, class T>
 __device__ __forceinline__ void nt_store(T *p, const T &v)
 {
-#ifdef IDSP_EXP_GENERIC_NT
-    if constexpr (!NT) {
-        *p = v;
-    } else if constexpr (sizeof(T) == 4) {
-        __builtin_nontemporal_store(__builtin_bit_cast(uint32_t, v), reinterpret_cast<uint32_t *>(p));
-    } else {
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        __builtin_nontemporal_store(__builtin_bit_cast(u32x2, v), reinterpret_cast<u32x2 *>(p));
-    }
-    return;
-#endif
     using W = typename WordsOf<int(sizeof(T))>::type;
     auto *g = reinterpret_cast<__attribute__((address_space(1))) W *>(reinterpret_cast<uintptr_t>(p));
     if constexpr (NT)
@@ -234,11 +217,7 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major(
     if constexpr (P::LDS_WORDS > 0) p.set_shared(ptab);
     p.load(prm, st, slanes, lane);
 
-#ifdef IDSP_NO_NT
-    constexpr bool kNT = false;
-#else
     constexpr bool kNT = P::COST <= 220;
-#endif
     // xl / yl: elements between consecutive frames of x / y (dense: lanes / IN_DIV and lanes — IN_DIV virtual
     // lanes share an input lane)
     const In *xp = x + lane / P::IN_DIV;
@@ -353,16 +332,6 @@ template <class P>
 struct LdsEligibleOf<P, std::void_t<decltype(P::LDS_ELIGIBLE)>> {
     static constexpr bool value = P::LDS_ELIGIBLE;
 };
-// Largest lanes-per-thread factor the LDS-DMA kernel is instantiated with for a processor (P::LDS_LPT_MAX; 1 = only
-// the one-lane-per-thread form).  Each step doubles the processor's state registers.
-template <class P, class = void>
-struct LdsLptMaxOf {
-    static constexpr int value = 1;
-};
-template <class P>
-struct LdsLptMaxOf<P, std::void_t<decltype(P::LDS_LPT_MAX)>> {
-    static constexpr int value = P::LDS_LPT_MAX;
-};
 template <class P, class = void>
 struct LdsRingOf {
     static constexpr int value = kLdsNB;
@@ -393,18 +362,6 @@ struct LdsRunOf<P, std::void_t<decltype(P::LDS_RUN)>> {
 #else
 #define IDSP_EXP_LM_ST_ON true
 #endif
-#ifndef IDSP_EXP_LDS_PLAIN_LD  // experiment: plain instead of nontemporal accesses in every instantiation of the LDS-DMA kernel
-#define IDSP_EXP_LDS_PLAIN_LD 0
-#endif
-#ifndef IDSP_EXP_LDS_PLAIN_ST
-#define IDSP_EXP_LDS_PLAIN_ST 0
-#endif
-#ifndef IDSP_XCDC_LOAD_NT
-#define IDSP_XCDC_LOAD_NT 1
-#endif
-#ifndef IDSP_XCDC_STORE_NT
-#define IDSP_XCDC_STORE_NT 1
-#endif
 template <int N, class F>
 __device__ __forceinline__ void static_for(F &&f)
 {
@@ -414,16 +371,9 @@ __device__ __forceinline__ void static_for(F &&f)
     }
 }
 
-// LPT ("lanes per thread") > 1: a workgroup owns 256 * LPT adjacent lanes and thread t runs the LPT independent
-// recurrences of lanes t, t + 256, ...  A tile is still TS one-KiB row segments (8 KiB; 16 KiB for LPT = 16) —
-// frames [v R, v R + R) x all LPT sub-blocks, R = TS / LPT — so ring bytes, barriers per sample and the vmcnt
-// bookkeeping are those of LPT = 1, and every workgroup sweeps whole (LPT KiB) row pieces in address order, so that a
-// launch of L lanes needs only L / (256 LPT) workgroups.  MEASURED AND NOT USED BY DEFAULT (no processor declares
-// LDS_LPT_MAX > 1): with the output right behind the input in one allocation the form runs 131072 lanes at 0.76-0.78
-// of the HBM peak and 262144 at 0.72 (one lane per thread on a persistent grid: 0.70 / 0.67), but over nine placements
-// of the output buffer it ranges 0.61-0.78 / 0.62-0.77 (mean 0.68 / 0.67) where the persistent one-lane form ranges
-// 0.69-0.75 / 0.65-0.69 (mean 0.72 / 0.68) — profiles/r02_exp_c5_place.jsonl, tools/exp_c5_place.hip.  The template
-// parameter stays for those tools and for IDSP_DIAG=1 IDSP_LDS_LPT experiments on processors that opt in.
+// One lane per thread: a workgroup of 256 threads owns a block of 256 adjacent lanes, and a tile is kLdsT frames of that
+// block: kLdsT one-KiB row segments.  (Several lanes per thread, a choice of block orders and plain instead of nontemporal
+// accesses were measured and retired: profiles/NOTES.md, "LDS-DMA kernel: forms retired".)
 // XCDC (round 3): rows that do not start on 64-byte boundaries — dense rows of 65000 or 65532 lanes, odd pitches.  The 1 KiB
 // row segments of adjacent lane blocks then share the 64-byte pieces at their boundaries, and with consecutive blocks dealt
 // round-robin to the 8 XCDs (each with its own L2) both halves of every shared piece are fetched — and partially written —
@@ -435,13 +385,7 @@ __device__ __forceinline__ void static_for(F &&f)
 // `dwordx4` request starts on a 64-byte boundary (the LDS-DMA destination is fixed by the hardware lane, so the row sits
 // rotated in LDS and the owning thread reads its column through the rotation) ran at 0.56 on EVERY pitch, aligned ones
 // included: the straddling quads were not the cost.
-// ILV (round 5, LPT > 1): the LPT sub-blocks of a workgroup are INTERLEAVED over the row — workgroup w of G owns the 256-lane
-// blocks w, w + G, w + 2G, ... — instead of adjacent.  One round of G workgroups then requests every row as ONE dense piece in
-// the very order the single-round C2 launch does (consecutive 1 KiB segments from consecutive workgroups, i.e. from the 8 XCDs
-// in turn), whatever the lane count: the launch sweeps memory front to back instead of visiting a 256 KiB panel of every row
-// per round (see launch_stream and profiles/NOTES.md, round 5: the strided panel walk is what holds C5 at 0.67-0.70; dense
-// rows run at 0.78 at a 32 GiB footprint as well).
-template <class P, int NB = LdsRingOf<P>::value, int LPT = 1, bool RUN = LdsRunOf<P>::value, bool XCDC = false, bool ILV = false>
+template <class P, int NB = LdsRingOf<P>::value, bool RUN = LdsRunOf<P>::value, bool XCDC = false>
 __global__ __launch_bounds__(kFmBlock) void stream_frame_major_lds(
     const typename P::Params prm, uint32_t *st, const typename P::In *x, typename P::Out *y,
     const size_t lanes, const size_t frames, const size_t xl, const size_t yl, const size_t slanes)
@@ -451,13 +395,11 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major_lds(
     using In = typename P::In;
     using Out = typename P::Out;
     static_assert(P::HAS_IN && P::IN_DIV == 1 && sizeof(In) == 4, "LDS path: one 4-byte input per lane and frame");
-    static_assert(LPT >= 1 && (LPT & (LPT - 1)) == 0, "LPT is a power of two");
     constexpr int OW = sizeof(Out) / 4, B = BatchOf<P>::value;
-    constexpr int TS = LPT > kLdsT ? LPT : kLdsT;  // 1 KiB row segments per tile
-    constexpr int R = TS / LPT;                    // frames per tile
-    constexpr int RPW = TS / 4;                    // segments per wave and tile
+    constexpr int TS = kLdsT;    // frames per tile = 1 KiB row segments per tile: segment g is frame g of the tile
+    constexpr int RPW = TS / 4;  // segments per wave and tile
     constexpr int kYoung = RPW * OW + (NB - 1) * (RPW + RPW * OW);
-    static_assert(kYoung <= 63 && TS % 4 == 0 && (LPT > 1 ? B == 1 : R % B == 0), "vmcnt range / tile shape");
+    static_assert(kYoung <= 63 && TS % 4 == 0 && TS % B == 0, "vmcnt range / tile shape");
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -468,90 +410,59 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major_lds(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)smem;
 
-    P p[LPT];
+    P p;
     if constexpr (P::LDS_WORDS > 0) {
         P::fill_shared(ptab, tid, kFmBlock);  // published by the first tile barrier
-#pragma unroll
-        for (int s = 0; s < LPT; s++) p[s].set_shared(ptab);
+        for (int once = 0; once < 1; once++) p.set_shared(ptab);  // one trip: see the state load below
     }
-#ifdef IDSP_EXP_LDS_SKEW  // experiment (tools/exp_c5_skew.sh): start-up stagger of persistent launches, ((b >> SHIFT) % MOD) x SKEW ticks of 10 ns
-    if ((lanes + size_t(kFmBlock) * LPT - 1) / (size_t(kFmBlock) * LPT) > gridDim.x) {
-        const long long d_ = (long long)(IDSP_EXP_LDS_SKEW) * ((blockIdx.x >> IDSP_EXP_LDS_SKEW_SHIFT) % IDSP_EXP_LDS_SKEW_MOD), t0_ = wall_clock64();
-        for (long long spins = d_ / 8 + 16; d_ && spins > 0 && wall_clock64() - t0_ < d_; spins--) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
-    // Persistent over lane blocks: workgroup w walks the (256 LPT)-lane blocks w, w + grid, w + 2 grid, ... one after
-    // the other (state load, the whole frame walk, state store per block).
-    constexpr size_t kBlockLanes = size_t(kFmBlock) * LPT;
-    // LPT == 1 with one-word outputs also takes a ragged last block (lanes % 256 != 0, lanes % 4 == 0: whole 16-byte pieces): a thread whose
+    // Persistent over lane blocks: a workgroup walks its 256-lane blocks one after the other (state load, the whole frame
+    // walk, state store per block).
+    // One-word outputs also take a ragged last block (lanes % 256 != 0, lanes % 4 == 0: whole 16-byte pieces): a thread whose
     // piece of the 1 KiB row segment lies beyond the last lane acts as a CLONE of an in-range thread — it requests
     // that thread's piece again and stores that thread's results to that thread's address (same bytes, twice) — so
     // the steady-state loop carries no predicate and every wave still issues exactly RPW loads and RPW * OW stores
     // per tile (the vmcnt bookkeeping below).  Its own column computes on whatever the clone's piece holds and is
     // dropped; only the state store is predicated.
-    const size_t nblocks = (lanes + kBlockLanes - 1) / kBlockLanes;  // LPT > 1: lanes % (256 LPT) == 0 (launcher)
+    const size_t nblocks = (lanes + size_t(kFmBlock) - 1) / size_t(kFmBlock);
     // (a workgroup that owns ADJACENT blocks instead — blocks [w rounds, (w + 1) rounds) — was measured slower: 0.58 vs
     // 0.68 of peak at 2^20 lanes, profiles/r02_exp_c5_matrix6.jsonl: the panel order keeps the concurrently active
     // columns in one contiguous 256 KiB piece of every row)
     // Order in which a persistent workgroup visits its column panels.  All workgroups advance through the frames in
-    // lockstep, so with the plain order (0) the whole launch touches the same few rows of ONE 256 KiB panel at any instant.
-    // Order 3 — the upper half of the grid starts half way through its panels — keeps two panels active: over nine
-    // placements of the output buffer 0.71-0.77 against 0.68-0.72 at 131072 lanes, 0.67-0.71 against 0.65-0.67 at 262144,
-    // 0.61-0.72 against 0.64-0.70 at 2^20 (profiles/r03_exp_c5_order.jsonl; tools/exp_c5_place.hip builds every order).
-    // Single-round launches (C2) are the same walk in every order.
-#ifndef IDSP_LDS_ORDER
-#define IDSP_LDS_ORDER 3
-#endif
-#if IDSP_LDS_ORDER == 0
-    for (size_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
-#else
-    // tools/exp_c5_place.hip: other orders in which a persistent workgroup visits its column panels (all workgroups advance
-    // through the frames in lockstep, so at any instant the launch touches the same few rows of ONE panel; these spread it
-    // over several).  1: rotated by XCD (blockIdx % 8); 2: rotated by groups of 32 adjacent workgroups; 3: the upper half of
-    // the grid starts half way; 4: odd workgroups walk the panels backwards.
+    // lockstep, so if workgroup w simply walked the blocks w, w + grid, w + 2 grid, ... the whole launch would touch the same
+    // few rows of ONE 256 KiB panel at any instant.  Here the upper half of the grid starts half way through its panels,
+    // which keeps two panels active: over nine placements of the output buffer 0.71-0.77 against 0.68-0.72 at 131072 lanes,
+    // 0.67-0.71 against 0.65-0.67 at 262144, 0.61-0.72 against 0.64-0.70 at 2^20 (profiles/r03_exp_c5_order.jsonl).
+    // Single-round launches (C2) are the same walk either way.
     const size_t rounds_ = (nblocks + gridDim.x - 1) / gridDim.x;
     for (size_t k_ = 0; k_ < rounds_; k_++) {
-    size_t rr_ = k_;
-    if (IDSP_LDS_ORDER == 1) rr_ = (k_ + (blockIdx.x & 7) * ((rounds_ + 7) / 8)) % rounds_;
-    if (IDSP_LDS_ORDER == 2) rr_ = (k_ + (blockIdx.x >> 5) * ((rounds_ + 7) / 8)) % rounds_;
-    if (IDSP_LDS_ORDER == 3) rr_ = (k_ + (blockIdx.x >= gridDim.x / 2 ? rounds_ / 2 : 0)) % rounds_;
-    if (IDSP_LDS_ORDER == 4) rr_ = (blockIdx.x & 1) ? rounds_ - 1 - k_ : k_;
-    // 5: as 3 with an ODD panel offset from 8 rounds up; 6: four quarter grids at offsets g (rounds / 4) + g; 7: eight groups at g (rounds / 8) + g
-    if (IDSP_LDS_ORDER == 5) rr_ = (k_ + (blockIdx.x >= gridDim.x / 2 ? rounds_ / 2 + (rounds_ >= 8 ? 1 : 0) : 0)) % rounds_;
-    if (IDSP_LDS_ORDER == 6) {
-        const size_t g_ = size_t(blockIdx.x) * 4 / gridDim.x;
-        rr_ = rounds_ >= 4 ? (k_ + g_ * (rounds_ / 4) + (rounds_ >= 8 ? g_ : 0)) % rounds_ : (k_ + (g_ >= 2 ? rounds_ / 2 : 0)) % rounds_;
-    }
-    if (IDSP_LDS_ORDER == 7) {
-        const size_t g_ = size_t(blockIdx.x) * 8 / gridDim.x;
-        rr_ = rounds_ >= 8 ? (k_ + g_ * (rounds_ / 8) + (rounds_ >= 16 ? g_ : 0)) % rounds_ : (k_ + (g_ >= 4 ? rounds_ / 2 : 0)) % rounds_;
-    }
+    const size_t rr_ = (k_ + (blockIdx.x >= gridDim.x / 2 ? rounds_ / 2 : 0)) % rounds_;
     // XCDC: workgroups are dealt to the XCDs round-robin (blockIdx % 8); give XCD j the j-th contiguous eighth of the blocks
     // (XCD j hosts the workgroups blockIdx = j, j + 8, ...: grid / 8 of them, one more on the first grid % 8 XCDs)
     const size_t q_ = gridDim.x / 8, r_ = gridDim.x % 8, j_ = blockIdx.x % 8;
     const size_t wg_ = XCDC ? j_ * q_ + (j_ < r_ ? j_ : r_) + blockIdx.x / 8 : blockIdx.x;
     const size_t blk = wg_ + rr_ * gridDim.x;
     if (blk >= nblocks) continue;
-#endif
-    static_assert(!ILV || (LPT > 1 && !XCDC), "ILV: interleaved sub-blocks of an LPT > 1 workgroup");
-    const size_t lane0 = ILV ? blk * size_t(kFmBlock) : blk * kBlockLanes;
-    const size_t sub = ILV ? nblocks * size_t(kFmBlock) : size_t(kFmBlock);  // lanes between the sub-blocks of this workgroup
+    const size_t lane0 = blk * size_t(kFmBlock);
     const size_t avail = lanes - lane0;  // lanes of this block that exist (>= 4)
-    const bool ragged_block = LPT == 1 && OW == 1 && avail < size_t(kFmBlock);
+    const bool ragged_block = OW == 1 && avail < size_t(kFmBlock);
     const int lid4 = ragged_block && size_t(lid * 4) >= avail ? int(size_t(lid * 4) % avail) : lid * 4;  // first lane of this thread's piece
     const bool lane_ok = !ragged_block || size_t(tid) < avail;
-#pragma unroll
-    for (int s = 0; s < LPT; s++) p[s].load(prm, st, slanes, lane_ok ? lane0 + size_t(s) * sub + tid : lanes - 1);
+    // set_shared above, the state load and the state store each sit in a loop of ONE trip on purpose: DO NOT FLATTEN them without
+    // a codegen diff (tools/diff_codegen.py) and a measurement.  As plain statements the load's address arithmetic dominates the
+    // store's, the optimiser shares it and then hoists the store's addresses out of `if (lane_ok)`, and that moves registers and
+    // spills in most instantiations (plain i32 DF1: only a branch in the drain loop; the lock-in processors: 2 VGPRs fewer, 2 SGPR
+    // spills more).  A helper function around the loop does not keep the code either.  The measured code is the one with the loops.
+    for (int once = 0; once < 1; once++) p.load(prm, st, slanes, lane_ok ? lane0 + tid : lanes - 1);
     // The state loads must have landed HERE, in a way the compiler's wait-count pass sees: it cannot see the DMA
     // requests of glds16(), and if it first needs a state register inside the steady-state loop it protects that use
     // with `s_waitcnt vmcnt(0)` on every iteration — which drains the whole prefetch ring each tile (0.52 instead of
     // 0.34 ms at C2 when a refactoring moved the first use).  vmcnt(0), expcnt / lgkmcnt untouched:
     __builtin_amdgcn_s_waitcnt(0x0F70);
 
-    const size_t ntiles = (frames + R - 1) / R;
-    const size_t nfull = frames / R;  // tiles [0, nfull) have all their rows
-    // segment g of a tile = frame g / LPT of the tile, sub-block g % LPT; a ragged tile holds nseg(v) segments
-    auto nseg = [&](size_t v) { return int((frames - v * R < size_t(R) ? frames - v * R : size_t(R)) * LPT); };
+    const size_t ntiles = (frames + TS - 1) / TS;
+    const size_t nfull = frames / TS;  // tiles [0, nfull) have all their rows
+    // a ragged tile holds nseg(v) segments
+    auto nseg = [&](size_t v) { return int(frames - v * TS < size_t(TS) ? frames - v * TS : size_t(TS)); };
     // Two forms of the per-tile addressing, chosen per processor (P::LDS_RUN) by measurement — these kernels sit on a
     // timing edge where the scalar instructions between the barriers decide how the DMA requests and the stores
     // interleave (profiles/r02_exp_c2_clamp*.jsonl, tools/exp_c2_clamp.sh: C2 shape, four placements of y):
@@ -560,7 +471,7 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major_lds(
     //   RUN = true   running ring slot, x / y pointers advanced per tile: the clamp forms (two more dependent
     //                operations per sample) run 0.77-0.78 at ring 5 this way in every placement, against 0.67-0.68
     //                (ring 5-7) or 0.67 / 0.75 by placement (ring 8) the other way.
-    const size_t xstep = size_t(R) * xl, ystep = size_t(R) * yl * OW;
+    const size_t xstep = size_t(TS) * xl, ystep = size_t(TS) * yl * OW;
     const In *xq = x + lane0 + lid4;                                          // RUN: tile about to be requested
     uint32_t *yq = reinterpret_cast<uint32_t *>(y) + lane0 * OW + lid4;       // RUN: tile about to be stored
     int slot_run = 0;                                                         // RUN: i % NB
@@ -571,11 +482,8 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major_lds(
         for (int j = 0; j < RPW; j++) {
             const int g = wave + 4 * j;
             if ((FULL || g < ns) && IDSP_EXP_LM_LD_ON) {
-                const In *src = RUN ? xq + size_t(g / LPT) * xl + (g % LPT) * sub : x + (v * R + g / LPT) * xl + lane0 + (g % LPT) * sub + lid4;
-                if constexpr ((XCDC && !IDSP_XCDC_LOAD_NT) || IDSP_EXP_LDS_PLAIN_LD)
-                    glds16_plain(src, lds_base + uint32_t((slot * TS + g) * kFmBlock * 4));
-                else
-                    glds16(src, lds_base + uint32_t((slot * TS + g) * kFmBlock * 4));
+                const In *src = RUN ? xq + size_t(g) * xl : x + (v * TS + g) * xl + lane0 + lid4;
+                glds16(src, lds_base + uint32_t((slot * TS + g) * kFmBlock * 4));
             }
         }
         if constexpr (RUN) xq += xstep;
@@ -592,12 +500,8 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major_lds(
 #pragma unroll
                 for (int h = 0; h < OW; h++) {
                     const u32x4 v4 = *reinterpret_cast<const u32x4 *>(o + (g * OW + h) * kFmBlock + lid4);
-                    uint32_t *dst = RUN ? yq + (size_t(g / LPT) * yl + (g % LPT) * sub) * OW + h * kFmBlock
-                                        : yw + ((v * R + g / LPT) * yl + lane0 + (g % LPT) * sub) * OW + h * kFmBlock + lid4;
-                    if constexpr ((XCDC && !IDSP_XCDC_STORE_NT) || IDSP_EXP_LDS_PLAIN_ST)
-                        *reinterpret_cast<u32x4 *>(dst) = v4;
-                    else
-                        __builtin_nontemporal_store(v4, reinterpret_cast<u32x4 *>(dst));
+                    uint32_t *dst = RUN ? yq + size_t(g) * yl * OW + h * kFmBlock : yw + ((v * TS + g) * yl + lane0) * OW + h * kFmBlock + lid4;
+                    __builtin_nontemporal_store(v4, reinterpret_cast<u32x4 *>(dst));
                 }
             }
         }
@@ -611,24 +515,24 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major_lds(
         const uint32_t *in = tin + (RUN ? slot_run : int(v % NB)) * TS * kFmBlock;
         uint32_t *o = tout + (v & 1) * TS * kFmBlock * OW;
         const int ns = FULL ? TS : nseg(v);
-        if constexpr (B > 1) {  // LPT == 1: segments are consecutive frames of one lane
+        if constexpr (B > 1) {
 #pragma unroll
             for (int r0 = 0; r0 < TS; r0 += B) {
                 if (!FULL && r0 >= ns) break;
                 typename P::Pre pre[B];
 #pragma unroll
                 for (int b = 0; b < B; b++)
-                    if (FULL || r0 + b < ns) pre[b] = p[0].pre(prm);
+                    if (FULL || r0 + b < ns) pre[b] = p.pre(prm);
 #pragma unroll
                 for (int b = 0; b < B; b++) {
                     const int r = r0 + b;
-                    if (FULL || r < ns) to_words<Out>(p[0].step(prm, __builtin_bit_cast(In, in[r * kFmBlock + tid]), pre[b]), o + (r * kFmBlock + tid) * OW);
+                    if (FULL || r < ns) to_words<Out>(p.step(prm, __builtin_bit_cast(In, in[r * kFmBlock + tid]), pre[b]), o + (r * kFmBlock + tid) * OW);
                 }
             }
         } else {
             static_for<TS>([&](auto gg) {
-                constexpr int g = decltype(gg)::value;  // static: the LPT states stay in registers
-                if (FULL || g < ns) to_words<Out>(p[g % LPT].step(prm, __builtin_bit_cast(In, in[g * kFmBlock + tid])), o + (g * kFmBlock + tid) * OW);
+                constexpr int g = decltype(gg)::value;
+                if (FULL || g < ns) to_words<Out>(p.step(prm, __builtin_bit_cast(In, in[g * kFmBlock + tid])), o + (g * kFmBlock + tid) * OW);
             });
         }
     };
@@ -661,9 +565,8 @@ __global__ __launch_bounds__(kFmBlock) void stream_frame_major_lds(
         store(i, Full{});
     }
     for (; i < ntiles; i++) slow_iter();
-#pragma unroll
-    for (int s = 0; s < LPT; s++)
-        if (lane_ok) p[s].store(prm, st, slanes, lane0 + size_t(s) * sub + tid);
+    for (int once = 0; once < 1; once++)  // one trip: see the state load
+        if (lane_ok) p.store(prm, st, slanes, lane0 + tid);
     // No barrier needed here: the next block's first lds_barrier() (after each wave's lgkmcnt wait) orders this
     // block's last output-tile reads before the compute() that overwrites the tile, and its first DMA rows only
     // touch input slots whose last readers passed the barrier after the final compute().
@@ -1598,7 +1501,7 @@ constexpr StreamTraits traits_of()
 {
     StreamTraits t;
     t.has_in = P::HAS_IN, t.in_div = P::IN_DIV, t.in_bytes = sizeof(typename P::In), t.out_bytes = sizeof(typename P::Out), t.cost = P::COST;
-    t.lds_eligible = LdsEligibleOf<P>::value, t.lds_lpt_max = LdsLptMaxOf<P>::value, t.lds_ring = LdsRingOf<P>::value;
+    t.lds_eligible = LdsEligibleOf<P>::value, t.lds_ring = LdsRingOf<P>::value;
     t.fm_staged = FmStagedOf<P>::value, t.lm_staged = LmStagedOf<P>::value, t.lm_one_form = LmOneFormOf<P>::value;
     t.sweep_max_lpt = SweepMaxLptOf<P>::value;
     return t;
@@ -1722,31 +1625,22 @@ template <class P>
 int launch_fm_lds(const StreamArgs<P> &a, const StreamPlan &p)
 {
     constexpr size_t ow = sizeof(typename P::Out) / 4;
-    constexpr int kMaxLpt = LdsLptMaxOf<P>::value;
-    auto go = [&](auto lpt_tag, auto deep, auto xcdc) {
-        constexpr int L = decltype(lpt_tag)::value;
+    auto go = [&](auto deep, auto xcdc) {
         constexpr bool DEEP = decltype(deep)::value, XCDC = decltype(xcdc)::value;
         constexpr int NB = DEEP ? 7 : LdsRingOf<P>::value;
         constexpr bool RUN = DEEP ? false : LdsRunOf<P>::value;
-        constexpr size_t ts = L > kLdsT ? L : kLdsT;
-        constexpr size_t bytes = (size_t(NB) * ts * kFmBlock + 2 * ts * kFmBlock * ow + P::LDS_WORDS) * 4;
-        if (int rc = ensure_dyn_lds<&stream_frame_major_lds<P, NB, L, RUN, XCDC>>(bytes)) return rc;
+        constexpr size_t bytes = (size_t(NB) * kLdsT * kFmBlock + 2 * size_t(kLdsT) * kFmBlock * ow + P::LDS_WORDS) * 4;
+        if (int rc = ensure_dyn_lds<&stream_frame_major_lds<P, NB, RUN, XCDC>>(bytes)) return rc;
         note_kernel(stream_plan_name(p), typeid(P).name());
-        hipLaunchKernelGGL((stream_frame_major_lds<P, NB, L, RUN, XCDC>), dim3(p.grid), dim3(kFmBlock), bytes, a.s, a.prm, a.st, a.x, a.y, a.lanes, a.frames, p.xl,
+        hipLaunchKernelGGL((stream_frame_major_lds<P, NB, RUN, XCDC>), dim3(p.grid), dim3(kFmBlock), bytes, a.s, a.prm, a.st, a.x, a.y, a.lanes, a.frames, p.xl,
                            p.yl, a.sp);
         return launch_status();
     };
     using Yes = std::true_type;
     using No = std::false_type;
-    if constexpr (kMaxLpt >= 4) {
-        if (p.lanes_per_thread == 4) return go(std::integral_constant<int, 4>{}, No{}, No{});
-    }
-    if constexpr (kMaxLpt >= 2) {
-        if (p.lanes_per_thread == 2) return go(std::integral_constant<int, 2>{}, No{}, No{});
-    }
-    if (p.xcdc) return go(std::integral_constant<int, 1>{}, Yes{}, Yes{});  // XCD-contiguous blocks: always the deep ring
-    if (p.deep_ring) return go(std::integral_constant<int, 1>{}, Yes{}, No{});
-    return go(std::integral_constant<int, 1>{}, No{}, No{});
+    if (p.xcdc) return go(Yes{}, Yes{});  // XCD-contiguous blocks: always the deep ring
+    if (p.deep_ring) return go(Yes{}, No{});
+    return go(No{}, No{});
 }
 
 template <class P>

@@ -29,16 +29,7 @@ __device__ __forceinline__ void glds16_s(const void *sbase, uint32_t voff, uint3
                  : "v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst))
                  : "memory");
 }
-// plain (cacheable) form: rows off the 64-byte grid, where neighbouring workgroups share lines (XCDC)
-__device__ __forceinline__ void glds16_plain(const void *gsrc, uint32_t lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst))
-                 : "memory");
-}
-// plain form with the SGPR base
+// plain (cacheable) form with the SGPR base: rows off the 64-byte grid, where neighbouring workgroups share lines
 __device__ __forceinline__ void glds16_s_plain(const void *sbase, uint32_t voff, uint32_t lds_dst)
 {
     unsigned keep;

@@ -27,7 +27,6 @@ struct StreamTraits {
     size_t in_bytes = 4, out_bytes = 4;
     int cost = 0;
     bool lds_eligible = true;     // LdsEligibleOf
-    int lds_lpt_max = 1;          // LdsLptMaxOf
     int lds_ring = 8;             // LdsRingOf
     bool fm_staged = true;        // FmStagedOf
     bool lm_staged = true;        // LmStagedOf
@@ -99,7 +98,6 @@ struct StreamSwitches {
     bool no_lds_path = false;                   // IDSP_NO_LDS_PATH: neither LDS-DMA kernel
     size_t lds_min_waves = thr::kLdsMinWaves;   // IDSP_LDS_MIN_WAVES
     size_t lds_max_waves = size_t(1) << 40;     // IDSP_LDS_MAX_WAVES
-    size_t lds_lpt = 0;                         // IDSP_LDS_LPT: lanes per thread
     size_t lds_grid = ~size_t(0);               // IDSP_LDS_GRID: workgroups at most (0: one per block)
     bool lds_no_xcdc = false;                   // IDSP_LDS_NO_XCDC: the plain block order on rows off the 64-byte grid
     bool fm_xcdc = false;                       // IDSP_FM_XCDC: XCD-contiguous blocks on the register-window kernel
@@ -140,7 +138,6 @@ StreamSwitches read_stream_switches(Env env)
     s.no_lds_path = on("IDSP_NO_LDS_PATH");
     s.lds_min_waves = size("IDSP_LDS_MIN_WAVES", s.lds_min_waves);
     s.lds_max_waves = size("IDSP_LDS_MAX_WAVES", s.lds_max_waves);
-    s.lds_lpt = size("IDSP_LDS_LPT", s.lds_lpt);
     s.lds_grid = size("IDSP_LDS_GRID", s.lds_grid);
     s.lds_no_xcdc = on("IDSP_LDS_NO_XCDC");
     s.fm_xcdc = on("IDSP_FM_XCDC");
@@ -216,7 +213,7 @@ enum class StreamForm {
     FmPair,          // stream_frame_major_pair
     FmSweep,         // stream_frame_major_sweep (fm_sweep.h): geom, xcdc
     FmStaged,        // stream_frame_major_staged: lanes_per_wave, grid, staged_flags
-    FmLds,           // stream_frame_major_lds: grid, lanes_per_thread, deep_ring, xcdc
+    FmLds,           // stream_frame_major_lds: grid, deep_ring, xcdc
     FmWindow,        // stream_frame_major (register window): grid, block, deep_window, xcdc
 };
 
@@ -228,7 +225,6 @@ struct StreamPlan {
     size_t head = 0, tail = 0;     // FmRoundsBeside
     bool head_swept = false;       // FmRoundsBeside: the whole rounds went to the sweep kernel — the caller sets it from the head's own plan
     unsigned grid = 0;             // workgroups (FmStaged, FmLds, FmWindow; the sweep's are geom.grid)
-    int lanes_per_thread = 1;      // FmLds
     bool deep_ring = false;        // FmLds: 7 tiles and the indexed form (persistent grids)
     bool xcdc = false;             // XCD-contiguous block order (FmSweep, FmLds, FmWindow)
     int staged_flags = 0;          // FmStaged: bit 0 XCD-contiguous lane blocks, bit 1 plain instead of nontemporal accesses
@@ -385,38 +381,23 @@ inline StreamPlan plan_frame_major(const StreamTraits &t, const StreamCall &c, c
         if (!sw.no_lds_path && eligible && waves >= sw.lds_min_waves && waves <= sw.lds_max_waves && (lanes % kPlanBlock == 0 || (ow == 1 && lanes % 4 == 0)) &&
             rows_ok) {
             // Grid (profiles/r02_exp_c5_*.jsonl).  Up to kLdsGridCap workgroups: one per 256-lane block.  Beyond: a persistent grid of <= 256
-            // workgroups (one per CU) that walks the lane blocks in column panels of equal rounds.  Two or four lanes per thread are available
-            // to processors that declare LDS_LPT_MAX; none does.
+            // workgroups (one per CU) that walks the lane blocks in column panels of equal rounds.
             const size_t nblocks = (lanes + kPlanBlock - 1) / kPlanBlock;
-            int lpt = 1;
-            if (lanes % kPlanBlock != 0) {
-                // ragged last block: one lane per thread only
-            } else if (sw.lds_lpt) {
-                lpt = int(sw.lds_lpt) > t.lds_lpt_max ? t.lds_lpt_max : int(sw.lds_lpt);
-                while (lpt > 1 && nblocks % size_t(lpt) != 0) lpt >>= 1;
-            } else {
-                for (int k = t.lds_lpt_max; k > 1; k >>= 1)
-                    if (nblocks % size_t(k) == 0 && nblocks / size_t(k) >= thr::kLdsLptMinGrid && nblocks / size_t(k) <= thr::kLdsLptMaxGrid) {
-                        lpt = k;
-                        break;
-                    }
-            }
-            const size_t wgs = nblocks / size_t(lpt);
-            size_t grid = wgs;
+            size_t grid = nblocks;
             if (sw.lds_grid != ~size_t(0)) {
-                if (sw.lds_grid && wgs > sw.lds_grid) grid = sw.lds_grid;
-            } else if (wgs > thr::kLdsGridCap) {
-                const size_t rounds = (wgs + 255) / 256;
-                grid = (wgs + rounds - 1) / rounds;
+                if (sw.lds_grid && nblocks > sw.lds_grid) grid = sw.lds_grid;
+            } else if (nblocks > thr::kLdsGridCap) {
+                const size_t rounds = (nblocks + 255) / 256;
+                grid = (nblocks + rounds - 1) / rounds;
             }
             p.form = StreamForm::FmLds;
-            p.grid = unsigned(grid), p.lanes_per_thread = lpt;
+            p.grid = unsigned(grid);
             // rows that do not start on 64-byte boundaries (dense 65000-lane tensors, odd pitches): adjacent lane blocks on one XCD
             // (0.67-0.71 of the peak on such rows instead of 0.58-0.64)
-            p.xcdc = lpt == 1 && !rows.grid64 && !sw.lds_no_xcdc;
+            p.xcdc = !rows.grid64 && !sw.lds_no_xcdc;
             // Ring depth: the processor's tuned depth for single-pass launches; persistent launches keep 7 tiles and the indexed form for
             // every processor — depths 3-5 lose 15-20 % there (profiles/r02_exp_c5_matrix7.jsonl: 0.56 vs 0.68 at 2^20 lanes)
-            p.deep_ring = lpt == 1 && grid < wgs && t.lds_ring != 7;
+            p.deep_ring = grid < nblocks && t.lds_ring != 7;
             return p;
         }
     }
@@ -467,10 +448,7 @@ inline const char *stream_plan_name(const StreamPlan &p)
         case StreamForm::FmStaged:
             return lw == 64 ? "stream_frame_major_staged[64 lanes/wave]" : lw == 32 ? "stream_frame_major_staged[32 lanes/wave]" : "stream_frame_major_staged[16 lanes/wave]";
         case StreamForm::FmLds:
-            return p.xcdc                    ? "stream_frame_major_lds[XCD-contiguous blocks]"
-                   : p.lanes_per_thread == 1 ? "stream_frame_major_lds"
-                   : p.lanes_per_thread == 2 ? "stream_frame_major_lds[2 lanes/thread]"
-                                             : "stream_frame_major_lds[4 lanes/thread]";
+            return p.xcdc ? "stream_frame_major_lds[XCD-contiguous blocks]" : "stream_frame_major_lds";
         case StreamForm::FmWindow: return p.xcdc ? "stream_frame_major[XCD-contiguous blocks]" : "stream_frame_major";
     }
     return "";

@@ -78,8 +78,8 @@ NOT_CONSULTED = {
     "kRoundsSplitMaxRounds": "ROUND_MAX_ROUNDS", "kStagedMinFrames": "STAGED_MIN_FRAMES", "kLmStagedMinRowBytes": "K_LM_RUN // 4 (lane_stream.h asserts the two equal)",
     # launch parameters that do not change the kernel's name (grid order, block size, prefetch depth), or that no shipped processor reaches
     "kStagedXcdcMinGrid": "the staged kernel's block order: not in the name", "kSweepXcdcMinGrid": "fewer than 8 workgroups of a sweep: below kSweepMinLanesFps",
-    "kSweepFpsMaxBlockLanes": "read directly by _launch_sweep (`g.bw <= 128`)", "kLdsLptMinGrid": "no processor declares LDS_LPT_MAX",
-    "kLdsLptMaxGrid": "no processor declares LDS_LPT_MAX", "kWindowBlockMinWaves": "the register-window kernel's block size: not in the name",
+    "kSweepFpsMaxBlockLanes": "read directly by _launch_sweep (`g.bw <= 128`)",
+    "kWindowBlockMinWaves": "the register-window kernel's block size: not in the name",
     "kWindowDeepMaxWaves": "the register-window kernel's prefetch depth: not in the name", "kWindowXcdcMinGrid": "IDSP_FM_XCDC only",
 }
 

@@ -31,13 +31,13 @@
 using namespace idsp;
 
 // The processors, by hand.  Values the processor does not declare are the detectors' defaults (lane_stream.h: LdsEligibleOf `COST <= 120`,
-// LdsLptMaxOf 1, LdsRingOf 8, FmStagedOf / LmStagedOf from the sample sizes, IN_DIV and BATCH; fm_sweep.h: SweepMaxLptOf `COST <= 120 ? 4 : 2`).
+// LdsRingOf 8, FmStagedOf / LmStagedOf from the sample sizes, IN_DIV and BATCH; fm_sweep.h: SweepMaxLptOf `COST <= 120 ? 4 : 2`).
 static StreamTraits traits(bool has_in, int in_div, size_t in_bytes, size_t out_bytes, int cost, bool lds_eligible, int lds_ring, bool fm_staged, bool lm_staged,
                            bool lm_one_form, int sweep_max_lpt)
 {
     StreamTraits t;
     t.has_in = has_in, t.in_div = in_div, t.in_bytes = in_bytes, t.out_bytes = out_bytes, t.cost = cost;
-    t.lds_eligible = lds_eligible, t.lds_lpt_max = 1, t.lds_ring = lds_ring;
+    t.lds_eligible = lds_eligible, t.lds_ring = lds_ring;
     t.fm_staged = fm_staged, t.lm_staged = lm_staged, t.lm_one_form = lm_one_form, t.sweep_max_lpt = sweep_max_lpt;
     return t;
 }
@@ -74,8 +74,8 @@ static void print_plan(const StreamTraits &t, StreamCall c, const StreamSwitches
     name = stream_plan_name(p);
     also = stream_plan_also(p) ? stream_plan_also(p) : "";
     char text[256];
-    snprintf(text, sizeof text, "grid=%u lanes_per_wave=%d lanes_per_thread=%d deep_ring=%d xcdc=%d staged_flags=%d block=%u deep_window=%d head=%zu tail=%zu sweep=%ux%dx%u,%u,fps%u",
-             p.grid, p.lanes_per_wave, p.lanes_per_thread, int(p.deep_ring), int(p.xcdc), p.staged_flags, p.block, int(p.deep_window), p.head, p.tail, p.geom.grid,
+    snprintf(text, sizeof text, "grid=%u lanes_per_wave=%d deep_ring=%d xcdc=%d staged_flags=%d block=%u deep_window=%d head=%zu tail=%zu sweep=%ux%dx%u,%u,fps%u",
+             p.grid, p.lanes_per_wave, int(p.deep_ring), int(p.xcdc), p.staged_flags, p.block, int(p.deep_window), p.head, p.tail, p.geom.grid,
              p.geom.lpt, p.geom.bw, p.geom.rounds, p.geom.fps);
     detail = text;
 }

@@ -2,7 +2,7 @@
 """Build check: no kernel of libidsp_hip.so may use scratch memory unless it is on the allow-list.
 
 Several kernels keep arrays in registers only because every loop over them is fully unrolled (`stage[NI]`, `ring[U]`,
-`held[][]`, `p[LPT]`, `cur/nxt[NS]`); when an unroll fails those arrays silently move to scratch, and the Makefile
+`held[][]`, the sweep kernel's `p[LPT]`, `cur/nxt[NS]`); when an unroll fails those arrays silently move to scratch, and the Makefile
 passes -Wno-pass-failed (the unroll warnings of the deliberately partially unrolled loops would drown everything else).
 This script is the signal instead: it takes the gfx950 code objects out of the shared library, reads each kernel's
 `.private_segment_fixed_size` / `.vgpr_spill_count` / `.sgpr_spill_count` from the code-object metadata and fails if a

@@ -9,10 +9,10 @@ O=gpurun_out/exp_c2_clamp.jsonl; : > $O
 for E in build/exp_c5 build/exp_c5_run build/exp_c5_clamp build/exp_c5_clamp_run; do
   echo "{\"binary\": \"$E\"}" >> $O
   for NB in 4 5 6 7 8 9 10; do
-    timeout 60 $E 65536 4096 0 0 $NB 0 0 1 >> $O
-    timeout 60 $E 65536 4096 0 0 $NB 0 -1 1 >> $O
-    timeout 60 $E 65536 4096 0 0 $NB 0 49152 1 >> $O
-    timeout 60 $E 65536 4096 0 0 $NB 1 0 1 >> $O
+    timeout 60 $E 65536 4096 0 0 $NB 0 0 >> $O
+    timeout 60 $E 65536 4096 0 0 $NB 0 -1 >> $O
+    timeout 60 $E 65536 4096 0 0 $NB 0 49152 >> $O
+    timeout 60 $E 65536 4096 0 0 $NB 1 0 >> $O
   done
 done
 cat $O

@@ -23,7 +23,7 @@ template <bool XCDC>
 float run(const P::Params &prm, uint32_t *st, const int32_t *x, int32_t *y, size_t lanes, size_t frames, size_t pitch)
 {
     constexpr size_t bytes = (size_t(7) * kLdsT * kFmBlock + 2 * kLdsT * kFmBlock) * 4;
-    auto k = stream_frame_major_lds<P, 7, 1, false, XCDC>;
+    auto k = stream_frame_major_lds<P, 7, false, XCDC>;
     CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
     const unsigned grid = unsigned((lanes + kFmBlock - 1) / kFmBlock);
     hipEvent_t a, b;

@@ -91,25 +91,11 @@ static void launch_old(const Ctx<P> &c, typename P::Out *y)
     constexpr size_t bytes = (size_t(NB) * kLdsT * kFmBlock + 2 * kLdsT * kFmBlock) * 4;
     static bool once = false;
     if (!once) {
-        CK(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_frame_major_lds<P, NB, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
+        CK(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_frame_major_lds<P, NB, false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
         once = true;
     }
-    hipLaunchKernelGGL((stream_frame_major_lds<P, NB, 1, false>), dim3(lib_grid(c.lanes)), dim3(kFmBlock), bytes, 0, c.prm, c.st, c.x, y, c.lanes, c.frames, c.lanes,
+    hipLaunchKernelGGL((stream_frame_major_lds<P, NB, false>), dim3(lib_grid(c.lanes)), dim3(kFmBlock), bytes, 0, c.prm, c.st, c.x, y, c.lanes, c.frames, c.lanes,
                        c.lanes, c.lanes);
-}
-
-template <class P, int NB, int LPT, bool ILV>
-static void launch_lpt(const Ctx<P> &c, typename P::Out *y)
-{
-    constexpr size_t ts = LPT > kLdsT ? LPT : kLdsT;
-    constexpr size_t bytes = (size_t(NB) * ts * kFmBlock + 2 * ts * kFmBlock) * 4;
-    static bool once = false;
-    if (!once) {
-        CK(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_frame_major_lds<P, NB, LPT, false, false, ILV>), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
-        once = true;
-    }
-    hipLaunchKernelGGL((stream_frame_major_lds<P, NB, LPT, false, false, ILV>), dim3(unsigned(c.lanes / kFmBlock / LPT)), dim3(kFmBlock), bytes, 0, c.prm, c.st, c.x, y,
-                       c.lanes, c.frames, c.lanes, c.lanes, c.lanes);
 }
 
 static SweepGeom g_geom;
@@ -274,23 +260,6 @@ static int run(const char *name, size_t lanes, size_t frames)
 #undef SW
         }
     }
-    auto lpt_sweeps = [&](auto lpt_tag) {
-        constexpr int L = decltype(lpt_tag)::value;
-        if (wgs % L || wgs / L < 128 || wgs / L > 1024) return;
-        char nm[64];
-        snprintf(nm, sizeof nm, "lds lpt%d adjacent nb7", L);
-        sweep(nm, unsigned(wgs / L), [&](T *y) { launch_lpt<P, 7, L, false>(c, y); });
-        snprintf(nm, sizeof nm, "lds lpt%d interleaved nb7", L);
-        sweep(nm, unsigned(wgs / L), [&](T *y) { launch_lpt<P, 7, L, true>(c, y); });
-        snprintf(nm, sizeof nm, "lds lpt%d interleaved nb5", L);
-        sweep(nm, unsigned(wgs / L), [&](T *y) { launch_lpt<P, 5, L, true>(c, y); });
-        snprintf(nm, sizeof nm, "lds lpt%d interleaved nb4", L);
-        sweep(nm, unsigned(wgs / L), [&](T *y) { launch_lpt<P, 4, L, true>(c, y); });
-    };
-    lpt_sweeps(std::integral_constant<int, 2>{});
-    lpt_sweeps(std::integral_constant<int, 4>{});
-    lpt_sweeps(std::integral_constant<int, 8>{});
-    lpt_sweeps(std::integral_constant<int, 16>{});
     std::vector<unsigned> grids{g1};
     if (wgs >= 512) grids.push_back(unsigned(std::min<size_t>(wgs, 512)));
     for (unsigned g : grids) {

@@ -56,8 +56,8 @@ int main()
     for (auto &v : hx) { s = s * 1664525u + 1013904223u; v = int32_t(s) >> 4; }
     CK(hipMemcpy(x, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
     constexpr size_t bytes = (size_t(7) * kLdsT * kFmBlock + 2 * kLdsT * kFmBlock) * 4;
-    auto k0 = stream_frame_major_lds<P, 7, 1, false, false>;
-    auto k1 = stream_frame_major_lds<P, 7, 1, false, true>;
+    auto k0 = stream_frame_major_lds<P, 7, false, false>;
+    auto k1 = stream_frame_major_lds<P, 7, false, true>;
     CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
     CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
     struct Sh { size_t lanes, pitch, off; };

@@ -92,9 +92,9 @@ void sweep(const char *name, const typename P::Params &prm, const Bufs &b, const
                 constexpr int NB = LdsRingOf<P>::value;
                 constexpr bool RUN = LdsRunOf<P>::value;
                 constexpr size_t bytes = (size_t(NB) * kLdsT * kFmBlock + 2 * kLdsT * kFmBlock + P::LDS_WORDS) * 4;
-                CK(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_frame_major_lds<P, NB, 1, RUN>), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
+                CK(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_frame_major_lds<P, NB, RUN>), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
                 auto lds = [&]() {
-                    hipLaunchKernelGGL((stream_frame_major_lds<P, NB, 1, RUN>), dim3(unsigned(sh.lanes / kFmBlock)), dim3(kFmBlock), bytes, 0, prm, b.stref,
+                    hipLaunchKernelGGL((stream_frame_major_lds<P, NB, RUN>), dim3(unsigned(sh.lanes / kFmBlock)), dim3(kFmBlock), bytes, 0, prm, b.stref,
                                        reinterpret_cast<const In *>(b.x), reinterpret_cast<Out *>(b.yref), sh.lanes, sh.frames, sh.pitch, sh.pitch, sh.lanes);
                 };
                 tlds = timeit(lds);

@@ -28,14 +28,14 @@ template <class P, int NB, bool RUN>
 float run1(const typename P::Params &prm, uint32_t *st, const typename P::In *x, typename P::Out *y)
 {
     constexpr size_t bytes = (size_t(NB) * kLdsT * kFmBlock + 2 * kLdsT * kFmBlock) * 4;
-    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_frame_major_lds<P, NB, 1, RUN>), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_frame_major_lds<P, NB, RUN>), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
     hipEvent_t a, b;
     CK(hipEventCreate(&a));
     CK(hipEventCreate(&b));
     std::vector<float> ts;
     for (int i = 0; i < 50; i++) {
         CK(hipEventRecord(a));
-        hipLaunchKernelGGL((stream_frame_major_lds<P, NB, 1, RUN>), dim3(kLanes / kFmBlock), dim3(kFmBlock), bytes, 0, prm, st, x, y, kLanes, kFrames, kLanes, kLanes, kLanes);
+        hipLaunchKernelGGL((stream_frame_major_lds<P, NB, RUN>), dim3(kLanes / kFmBlock), dim3(kFmBlock), bytes, 0, prm, st, x, y, kLanes, kFrames, kLanes, kLanes, kLanes);
         CK(hipEventRecord(b));
         CK(hipEventSynchronize(b));
         float ms;
