@@ -220,7 +220,7 @@ inline int ensure_dyn_lds(size_t bytes)
     return IDSP_OK;
 }
 
-// The start-up stagger of the line-wise LaneMajor kernels (lockin_waves.h "lanes in phase", dds.hip) spaces the CUs of an XCD by
+// The start-up stagger of the line-wise LaneMajor kernels (lockin_waves.h "lanes in phase", fm_disc.hip) spaces the CUs of an XCD by
 // ticks of the 100 MHz wall clock and relies on workgroup b running on XCD b % 8 of a 256-CU part: tuned on MI355X (gfx950) in SPX
 // mode.  On any other part or partition the wait would be pure added latency, so it is armed only there (cached per device).
 inline bool stagger_tuned_device()

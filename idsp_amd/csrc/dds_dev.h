@@ -8,6 +8,7 @@
 #include "biquad_sections.h"
 #include "lane_stream.h"
 #include "lockin_plan.h"
+#include "readout_plan.h"
 
 namespace idsp {
 namespace {
@@ -37,6 +38,18 @@ inline LockinPlan lockin_plan_for(LockinArms arms, LockinLo lo, int readout, int
     c.x = reinterpret_cast<uintptr_t>(x), c.y = reinterpret_cast<uintptr_t>(y);
     c.tuned_device = layout == IDSP_LANE_MAJOR && stagger_tuned_device();  // read for the LaneMajor input forms only
     return plan_lockin(c, lockin_switches());
+}
+
+// The kernel-selection switches of idsp_fm_disc_i32 and of idsp_dds_i32 (readout_plan.h), read once per process in the same way
+inline const FmDiscSwitches &fm_disc_switches()
+{
+    static const FmDiscSwitches sw = read_fm_disc_switches(diag_env);
+    return sw;
+}
+inline const DdsSwitches &dds_switches()
+{
+    static const DdsSwitches sw = read_dds_switches(diag_env);
+    return sw;
 }
 
 // f(N, K) / f(NS) with the configuration as compile-time constants: `[Lowpass<N>; K]`, 1..4 biquad sections (callers have checked n)

@@ -3,8 +3,9 @@
 // comes from is named, profiles/NOTES.md has the numbers, and tests/test_gpu_dispatch_table.py pins the kernel taken at every BASELINE
 // shape and on both sides of every cliff listed here; tests/test_stream_plan.py pins the same table and both sides of every threshold without
 // a GPU, through `plan_stream` (stream_plan.h), which is the one reader of what follows — but for the lock-in section, whose one reader is
-// `plan_lockin` (lockin_plan.h; tests/test_lockin_plan.py pins both sides of each of its names the same way), and for the half-band and Cic
-// sections, read by `plan_hbf` / `plan_cic` (resample_plan.h; tests/test_resample_plan.py).
+// `plan_lockin` (lockin_plan.h; tests/test_lockin_plan.py pins both sides of each of its names the same way), for the half-band and Cic
+// sections, read by `plan_hbf` / `plan_cic` (resample_plan.h; tests/test_resample_plan.py), and for the last section, read by `plan_fm_disc` /
+// `plan_dds` (readout_plan.h; tests/test_fm_disc_plan.py), which also read the stagger section's window and its kFmDiscStaggerTicks.
 #pragma once
 
 #include <cstddef>
@@ -63,7 +64,7 @@ constexpr size_t kLmStaged64Lanes = 49152, kLmStaged32Lanes = 24576;
 // ... from this many bytes per row on the wider side (a quarter of the staged kernel's 512-byte run: below, the tile kernel has less to set up)
 constexpr size_t kLmStagedMinRowBytes = 128;
 
-// ---- start-up stagger of the line-wise LaneMajor kernels (lockin_waves.h, dds.hip; MI355X in SPX mode only: stagger_tuned_device()) --
+// ---- start-up stagger of the line-wise LaneMajor kernels (lockin_waves.h, fm_disc.hip; MI355X in SPX mode only: stagger_tuned_device()) --
 constexpr unsigned kStaggerMinWorkgroups = 512;                     // launches of at least two workgroups per CU
 constexpr size_t kStaggerMinFrames = 2048, kStaggerMaxFrames = 8192;  // long enough to pay, short enough not to drift apart anyway
 constexpr unsigned kLockinStaggerTicks = 600, kFmDiscStaggerTicks = 1200;  // 10 ns ticks between the four CU groups of an XCD
@@ -109,6 +110,27 @@ constexpr size_t kLockinB16MinLanes = 49152, kLockinB16MaxLanes = 65536;
 constexpr size_t kLockinWavesMaxLanes = 268435456;
 // LaneMajor rows that are not whole batches: body on the multi-wave kernel + tail on a stream kernel from this many frames
 constexpr size_t kLockinTailMinFrames = 32;
+
+// ---- FM discriminator and DDS (plan_fm_disc / plan_dds, readout_plan.h; tests/test_fm_disc_plan.py pins both sides of each name) -------
+// (Fixed-width types, as in the half-band section.  plan_fm_disc also reads kPieceBytes for the two addresses and the stagger section.)
+// FrameMajor role waves (fm_disc_waves_kernel, fm_disc.hip) UP TO this many lanes: beyond, the stream kernel has two waves per SIMD itself
+// and fewer instructions per sample (no LDS hand-over, no second read of the previous row): 131072 lanes 1.40 ms against 1.52
+// (profiles/r03_perf_fm_disc.jsonl)
+constexpr uint64_t kFmDiscWavesMaxLanes = 81920;
+// ... from this many frames: what one front wave takes of a tile
+constexpr uint64_t kFmDiscFmMinFrames = 8;
+// LaneMajor role waves (fm_disc_waves_lm_kernel) take whole tiles of this many frames, so rows of at least one ...
+constexpr uint64_t kFmDiscLmTile = 32;
+// ... of any multiple of this many frames (the last 16 of a row that is not whole tiles go to the tile kernel behind): multiples of 16 keep
+// the input lines on the 128-byte grid; rows off it lose more to straddled lines than the role waves win (65536 lanes x 4100 / 4104 / 4124
+// frames: 1.52 / 1.37 / 1.51 ms against 1.29 on the tile kernel; 4112 frames: 1.01)
+constexpr uint64_t kFmDiscLmRowMultiple = 16;
+// ... and keep 32-bit thread offsets inside a row: fewer lanes than this (2^28)
+constexpr uint64_t kFmDiscLmMaxLanes = 268435456;
+// DDS: the full-circle cossin table (16 KiB of LDS, filled at the start of every workgroup) for FrameMajor calls from this many frames,
+// on the two-threads-per-lane form only (up to kSplitMaxLanes, lock-in section): one thread per lane runs 65536 lanes x 4096 in 0.36-0.37 ms
+// on the 512-byte table and 0.46 on this one (profiles/r03_perf_dds_circle.jsonl, r03_perf_dds_one_circle.jsonl)
+constexpr uint64_t kDdsCircleMinFrames = 256;
 
 }  // namespace thr
 }  // namespace idsp

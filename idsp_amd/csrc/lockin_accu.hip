@@ -1,7 +1,7 @@
 // lockin_accu.hip — idsp_lockin_i32_accu_process: the external-LO lock-in with lowpass arms (src/lockin.rs:17-39) on the LO that
 // idsp_accu_lo_i32 would write for the same `Accu` rows (src/accu.rs:34-54, src/complex.rs:237-240), evaluated inside the kernel
 // (lockin_accu_procs.h) — the 8 bytes per sample of LO are neither written nor read.  A translation unit of its own: the sixteen
-// launch_stream instantiations compile beside lockin_generic.hip and dds.hip, not inside them.
+// launch_stream instantiations compile beside lockin_generic.hip and lockin_phase.hip, not inside them.
 #include "lockin_accu_procs.h"
 
 namespace idsp {

@@ -279,7 +279,7 @@ int idsp_lockin_i32_biquad_process(const idsp_biquad_i32 *sections, size_t n, vo
     const LockinPlan plan = lockin_plan_for(LockinArms::Biquad, LockinLo::Phase, MODE_IQ, 0, 0, x, y, lanes, frames, layout);
     if (plan.form == LockinForm::Stream) return on_stream(x, y, frames, 0);
     // WavesTail: the whole batches of every LaneMajor row on the multi-wave kernel at the call's row pitch, the last frames % 16 on the
-    // stream kernel behind it (as for the lowpass arms, dds.hip)
+    // stream kernel behind it (as for the lowpass arms, lockin_phase.hip)
     const bool tail = plan.form == LockinForm::WavesTail;
     rc = lockin_waves_biquad_iq(sections, n, state, x, y, lanes, plan, s, tail ? frames : 0);
     if (rc || !tail) return rc;

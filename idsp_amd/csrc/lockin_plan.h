@@ -1,7 +1,7 @@
 // lockin_plan.h — which kernel a call of one of the eight lock-in entries takes, as ONE pure function (as stream_plan.h is for launch_stream).
 //
 // `plan_lockin` reads the call (LockinCall) and the diagnostic switches (LockinSwitches) and returns the decision (LockinPlan): the entries
-// (dds.hip, lockin_generic.hip) and the launchers of lockin_waves.h do what it says; tests/test_lockin_plan.py runs the same function
+// (lockin_phase.hip, lockin_generic.hip) and the launchers of lockin_waves.h do what it says; tests/test_lockin_plan.py runs the same function
 // through tests/cpp/stream_plan_cli.cpp without a GPU.  No HIP here: plain C++17.  Thresholds: dispatch_thresholds.h, "lock-in".
 #pragma once
 
@@ -40,7 +40,7 @@ struct LockinSwitches {
     bool no_skew = false;        // IDSP_LOCKIN_NO_SKEW: no start-up stagger
     bool no_dma = false;         // IDSP_LOCKIN_NO_DMA: register-prefetch input
     int batch = 0;               // IDSP_LOCKIN_B = 8 / 16 forces a batch length (FrameMajor DMA form)
-    size_t split_max_lanes = thr::kSplitMaxLanes;  // IDSP_SPLIT_MAX_LANES (idsp_dds_i32 reads it too)
+    size_t split_max_lanes = thr::kSplitMaxLanes;  // IDSP_SPLIT_MAX_LANES (read_dds_switches of readout_plan.h reads it too, for idsp_dds_i32)
 };
 
 // `env(name)`: the variable's text or NULL (the library passes `diag_env`)
@@ -129,7 +129,7 @@ inline LockinPlan plan_lockin(const LockinCall &c, const LockinSwitches &sw)
     if (!p.waves) {
         // LaneMajor rows that are not whole 16-frame batches (round 4): the multi-wave kernel takes the whole batches of every row at the call's
         // row pitch and a stream kernel the last frames % 16 behind it (same stream; the state carries over as between two calls).  Rows
-        // must keep their 16-byte alignment: frames % 4 == 0.  (IDSP_LOCKIN_NO_LM_TAIL: lockin_lm_body of dds.hip read it, lm_body of
+        // must keep their 16-byte alignment: frames % 4 == 0.  (IDSP_LOCKIN_NO_LM_TAIL: lockin_lm_body of what is now lockin_phase.hip read it, lm_body of
         // lockin_generic.hip did not.)  The tail is never the two-thread split.
         const bool tail = lm && !(lowpass_phase && sw.no_lm_tail) && c.frames >= thr::kLockinTailMinFrames && c.frames % 4 == 0 && c.frames % kLwBLm != 0;
         p.body = tail ? c.frames - c.frames % kLwBLm : 0;

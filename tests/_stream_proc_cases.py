@@ -66,8 +66,8 @@ NOT_CONSULTED = {
     "kSweepMinLptSeveralSweeps": "several sweeps per launch (more than 256 x 4 x 256 lanes); read directly by sweep_takes",
     "kPairMaxCost": "a compile-time condition on COST, read directly (no side of it depends on the shape)",
     "kDuoMinLanes": "two-wave chain kernel: biquad chains only", "kDuo4MaxLanes": "two-wave chain kernel: biquad chains only",
-    "kStaggerMinWorkgroups": "lockin_waves.h / dds.hip", "kStaggerMinFrames": "lockin_waves.h / dds.hip",
-    "kStaggerMaxFrames": "lockin_waves.h / dds.hip", "kLockinStaggerTicks": "lockin_waves.h", "kFmDiscStaggerTicks": "dds.hip",
+    "kStaggerMinWorkgroups": "lockin_plan.h / readout_plan.h", "kStaggerMinFrames": "lockin_plan.h / readout_plan.h",
+    "kStaggerMaxFrames": "lockin_plan.h / readout_plan.h", "kLockinStaggerTicks": "lockin_plan.h", "kFmDiscStaggerTicks": "readout_plan.h (fm_disc.hip)",
     # the lock-in entries' own dispatch: tests/_lockin_plan_cases.py holds a row on each side of every one of them
     "kSplitMaxLanes": "lockin_plan.h", "kLockinSixWavesMaxLanes": "lockin_plan.h", "kLockinStagesOneGroupMaxLanes": "lockin_plan.h",
     "kLockinSixWavesArmWeight": "lockin_plan.h", "kLockinB16MinLanes": "lockin_plan.h", "kLockinB16MaxLanes": "lockin_plan.h",

@@ -17,6 +17,11 @@
 //           (hbf_plan_name), a tab, `form= grid=`
 //   cic <dec|int> <32|64> <order> <rate> <lanes> <frames> <FM|LM> <x mod 16> <y mod 16> [IDSP_SWITCH=value ...]
 //        -> `plan_cic` for a call of idsp_cic_<dec|int>_i<32|64>: cic_plan_name, a tab, `form= ppt= vpc= grid=`
+//   fm_disc <lanes> <frames> <FM|LM> <x mod 16> <y mod 16> [tuned] [IDSP_SWITCH=value ...]
+//        -> `plan_fm_disc` (idsp_amd/csrc/readout_plan.h) for a call of idsp_fm_disc_i32: the start of what idsp_last_kernel() reports
+//           (fm_disc_plan_name), a tab, `form= waves= grid= body= tail= skew= shift= mod=`
+//   dds <lanes> <frames> <FM|LM> [IDSP_SWITCH=value ...]
+//        -> `plan_dds` for a call of idsp_dds_i32: `stream_<Processor>`, a tab, `split= circle=`
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -25,6 +30,7 @@
 #include <string>
 
 #include "../../idsp_amd/csrc/lockin_plan.h"
+#include "../../idsp_amd/csrc/readout_plan.h"
 #include "../../idsp_amd/csrc/resample_plan.h"
 #include "../../idsp_amd/csrc/stream_plan.h"
 
@@ -80,7 +86,7 @@ static void print_plan(const StreamTraits &t, StreamCall c, const StreamSwitches
     detail = text;
 }
 
-// The lock-in entries, by hand: arms and LO of each, the stream processor it runs (dds.hip, lockin_generic.hip, lockin_accu.hip) and the
+// The lock-in entries, by hand: arms and LO of each, the stream processor it runs (lockin_phase.hip, lockin_generic.hip, lockin_accu.hip) and the
 // name of its arm functor on the multi-wave kernel (`Bank::name()`: lockin_waves_biquad.hip, lockin_waves_lo.hip; none for `LpBank`)
 static bool lockin_line(std::istringstream &in, const LockinSwitches &sw, bool tuned, const std::string &entry, std::string &out)
 {
@@ -154,6 +160,45 @@ static bool resample_line(const std::string &cmd, std::istringstream &in, std::m
     return true;
 }
 
+// the two read-out verbs: the shape words of the line, `tuned`, then the switches
+template <class Env>
+static bool readout_line(const std::string &cmd, std::istringstream &in, std::map<std::string, std::string> &env, Env getenv_, std::string &out)
+{
+    std::string layout, word;
+    size_t lanes = 0, frames = 0, xo = 0, yo = 0;
+    bool tuned = false;
+    in >> lanes >> frames >> layout;
+    if (cmd == "fm_disc") in >> xo >> yo;
+    if (!in || (layout != "FM" && layout != "LM")) return false;
+    while (in >> word) {
+        if (word == "tuned" && cmd == "fm_disc")
+            tuned = true;
+        else if (word.find('=') == std::string::npos)
+            return false;
+        else
+            env[word.substr(0, word.find('='))] = word.substr(word.find('=') + 1);
+    }
+    char text[256];
+    if (cmd == "fm_disc") {
+        FmDiscCall c;
+        c.lanes = lanes, c.frames = frames, c.layout = layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR;
+        c.x = (uintptr_t(1) << 32) + xo, c.y = (uintptr_t(1) << 33) + yo, c.tuned_device = tuned;
+        static const char *const kForms[4] = {"Stream", "WavesFm", "WavesLm", "WavesLmTail"};
+        const FmDiscPlan p = plan_fm_disc(c, read_fm_disc_switches(getenv_));
+        snprintf(text, sizeof text, "%s\tform=%s waves=%d grid=%u body=%zu tail=%zu skew=%u shift=%u mod=%u", fm_disc_plan_name(p), kForms[int(p.form)], p.front_waves,
+                 p.grid, p.body, p.tail, p.skew, p.skew_shift, p.skew_mod);
+    } else {
+        DdsCall c;
+        c.lanes = lanes, c.frames = frames, c.layout = layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR;
+        const DdsPlan p = plan_dds(c, read_dds_switches(getenv_));
+        // the stream processor the entry instantiates for the plan (dds.hip), by hand
+        const char *proc = p.circle ? "DdsSplitProcT<true>" : p.split ? "DdsSplitProcT<false>" : "DdsProcT<false>";
+        snprintf(text, sizeof text, "stream_<%s>\tsplit=%d circle=%d", proc, int(p.split), int(p.circle));
+    }
+    out = text;
+    return true;
+}
+
 int main()
 {
     std::string line;
@@ -206,6 +251,12 @@ int main()
         } else if (cmd == "hbf" || cmd == "cic") {
             std::string out;
             if (resample_line(cmd, in, env, getenv_, out))
+                printf("%s\n", out.c_str());
+            else
+                printf("error: %s\n", line.c_str());
+        } else if (cmd == "fm_disc" || cmd == "dds") {
+            std::string out;
+            if (readout_line(cmd, in, env, getenv_, out))
                 printf("%s\n", out.c_str());
             else
                 printf("error: %s\n", line.c_str());

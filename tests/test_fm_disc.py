@@ -82,7 +82,7 @@ FORCED_WAVES = os.environ.get("IDSP_FM_DISC_WAVES") if os.environ.get("IDSP_DIAG
 
 @pytest.mark.gpu
 def test_fm_disc_role_waves_frame_major(gpu):
-    """`fm_disc_waves_kernel` (idsp_amd/csrc/dds.hip): the discriminator of a tile's frames on four front waves, the deemphasis
+    """`fm_disc_waves_kernel` (idsp_amd/csrc/fm_disc.hip): the discriminator of a tile's frames on four front waves, the deemphasis
     biquad on a fifth.  Frame counts around the 32-frame tiles and the 8-frame wave shares, lanes around the 64-lane workgroups,
     continuation across calls (the state's `prev` feeds frame 0), lanes that start without a previous sample."""
     ob, gb = OracleBackend(), GpuBackend()

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Whole-engine variants with one object (UNIT, default biquad_i32_df1: the LaneMajor biquad without its loads / stores) rebuilt with -D switches
+# Whole-engine variants with one object (UNIT, default biquad_i32_df1: the LaneMajor biquad without its loads / stores; UNIT=fm_disc with
+# VARIANTS of -DIDSP_FMD_ABL_NOSTORE / -DIDSP_FMD_ABL_NOLOAD: the FM discriminator's role kernels) rebuilt with -D switches
 #   bash tools/exp_lm_ablate.sh build ; gpurun -- 'bash tools/exp_lm_ablate.sh run'
 set -u
 UNIT=${UNIT:-biquad_i32_df1}
