@@ -412,6 +412,15 @@ BIQUAD_I16 = {
     "biquad_i16_df1_clamp": (_I, [_P, _SZ, _P, _P, _SZ, _P, _SZ, _SZ, _SZ, _I, _P]),
 }
 UTILS.update(BIQUAD_I16)
+# ... and its per-lane coefficient banks.  A table of its own beside BIQUAD_I16 (tests/test_biquad_i16_host.py pins that one's keys),
+# merged into UTILS the same way: no twin in the checker library, parity rests on tests/_biquad_i16_bylane_spec.py
+BIQUAD_I16_BYLANE = {
+    # coef, frac, n, state, x, x_pitch, y, y_pitch, lanes, frames, layout, stream
+    "biquad_i16_df1_bylane": (_I, [_P, _I, _SZ, _P, _P, _SZ, _P, _SZ, _SZ, _SZ, _I, _P]),
+    "biquad_i16_df1_clamp_bylane": (_I, [_P, _I, _SZ, _P, _P, _SZ, _P, _SZ, _SZ, _SZ, _I, _P]),
+    "biquad_i16_bank_from_sos": (_I, [_P, _SZ, _SZ, _I, _SZ, _P]),  # sos, lanes, n, frac, cv, coef (host)
+}
+UTILS.update(BIQUAD_I16_BYLANE)
 
 SHARD_FN = C.CFUNCTYPE(_I, _P, _I, _SZ, _SZ, _P)  # idsp_shard_fn
 

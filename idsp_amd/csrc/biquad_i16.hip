@@ -1,5 +1,6 @@
 // biquad_i16.hip — `Biquad<Q16<F>>` / `BiquadClamp<Q16<F>, i16>` x `DirectForm1<i16>` (src/iir/biquad.rs:366-404): the host side of
-// the kernels of biquad_i16_kernels.h and the coefficient ingestion.  The entries take row pitches and any 2-byte-aligned x and y:
+// the shared-coefficient kernels of biquad_i16_kernels.h and the coefficient ingestion, of one section and of a by-lane bank (whose
+// entries are in biquad_i16_bylane.hip).  The entries take row pitches and any 2-byte-aligned x and y:
 // i16 rows with an odd row length are the normal case, and the pitch is how a caller keeps them on the 4-byte grid where the fast
 // forms run (biquad_i16_plan.h).
 #include <cmath>
@@ -27,16 +28,6 @@ inline void fill(Sec &d, const idsp_biquad_clamp_i16 &c)
 {
     pack(d, c.ba, c.frac);
     d.u = c.u, d.mn = c.min, d.mx = c.max;
-}
-
-inline Switches switches()
-{
-    static const Switches sw = [] {
-        Switches s;
-        if (const char *e = diag_env("IDSP_BQ16_FM_BLOCK")) s.fm_block = unsigned(atoi(e));
-        return s;
-    }();
-    return sw;
 }
 
 // sections first .. first + N - 1 in one launch
@@ -108,6 +99,14 @@ int16_t to_q16(double v, int frac)
     return int16_t(s);
 }
 
+// [b0, b1, b2, a0, a1, a2] -> ba: biquad.rs:551-559, each value through to_q16
+void ba_from_sos(const double *sos, int frac, int16_t *ba)
+{
+    const double a0 = 1.0 / sos[3];
+    const double v[5] = {sos[0] * a0, sos[1] * a0, sos[2] * a0, -sos[4] * a0, -sos[5] * a0};
+    for (int i = 0; i < 5; i++) ba[i] = to_q16(v[i], frac);
+}
+
 }  // namespace
 }  // namespace idsp
 
@@ -119,10 +118,24 @@ int idsp_biquad_i16_from_sos(const double sos[6], int frac, idsp_biquad_i16 *out
 {
     if (!sos || !out) return fail(IDSP_EINVAL, "sos or out is NULL");
     if (frac < 0 || frac > 31) return fail(IDSP_EINVAL, "frac = %d not in 0..31", frac);
-    const double a0 = 1.0 / sos[3];  // biquad.rs:551-559
-    const double ba[5] = {sos[0] * a0, sos[1] * a0, sos[2] * a0, -sos[4] * a0, -sos[5] * a0};
-    for (int i = 0; i < 5; i++) out->ba[i] = to_q16(ba[i], frac);
+    ba_from_sos(sos, frac, out->ba);
     out->frac = int16_t(frac);
+    return IDSP_OK;
+}
+
+int idsp_biquad_i16_bank_from_sos(const double *sos, size_t lanes, size_t n, int frac, size_t cv, int16_t *coef)
+{
+    if (frac < 0 || frac > 31) return fail(IDSP_EINVAL, "frac = %d not in 0..31", frac);
+    if (cv != 5 && cv != 8) return fail(IDSP_EINVAL, "cv = %zu is neither 5 (ba) nor 8 (ba, u, min, max)", cv);
+    if (n > IDSP_MAX_SECTIONS) return fail(IDSP_EINVAL, "n = %zu sections > IDSP_MAX_SECTIONS", n);
+    if (lanes == 0 || n == 0) return IDSP_OK;
+    if (!sos || !coef) return fail(IDSP_EINVAL, "sos or coef is NULL");
+    for (size_t l = 0; l < lanes; l++)
+        for (size_t k = 0; k < n; k++) {
+            int16_t sec[8] = {0, 0, 0, 0, 0, 0, INT16_MIN, INT16_MAX};  // u, min, max: BiquadClamp::default (biquad.rs:159-171)
+            ba_from_sos(sos + (l * n + k) * 6, frac, sec);
+            for (size_t v = 0; v < cv; v++) coef[(k * cv + v) * lanes + l] = sec[v];
+        }
     return IDSP_OK;
 }
 

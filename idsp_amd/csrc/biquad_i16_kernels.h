@@ -45,6 +45,17 @@ struct Params {
     Sec sec[N];
 };
 
+// the measurement switches of biquad_i16_plan.h, read once per process
+inline Switches switches()
+{
+    static const Switches sw = [] {
+        Switches s;
+        if (const char *e = diag_env("IDSP_BQ16_FM_BLOCK")) s.fm_block = unsigned(atoi(e));
+        return s;
+    }();
+    return sw;
+}
+
 __device__ __forceinline__ int32_t lo16(uint32_t w) { return int32_t(int16_t(w)); }
 __device__ __forceinline__ int32_t hi16(uint32_t w) { return int32_t(w) >> 16; }
 typedef short short2v __attribute__((ext_vector_type(2)));
@@ -232,6 +243,150 @@ __global__ __launch_bounds__(kWave) void biquad_i16_lane_major(const Params<N> p
     }
     if (active) p.store(st, lanes, lane);
 }
+
+// ------------------------------------------------------------------- BY LANE
+// `ByLane<[C; N]>` (dsp-process/src/compose.rs:363-390): lane l runs configuration l on state l.  The same step and the same two
+// walkers; only the section's home changes, from the kernel arguments (SGPRs) to the thread's registers.  `coef`: i16 planes, value v
+// of section k of lane l at coef[(k * CV + v) * lanes + l], CV = 5 {b0, b1, b2, a1, a2} or, CLAMP, 8 {.., u, min, max}
+// (include/idsp_hip.h).  A thread reads its own lane of every plane once, before the first frame: 16-bit loads, 128 contiguous bytes per
+// wave and plane wherever the plane begins (an odd lane count puts every other plane off the 4-byte grid), and packs them into the
+// words of `Sec`.  A thread WITHOUT a lane must not come here: the planes end with the last lane.
+// b0 for the odd sample of a dword (`step<true>`) is a second register, b0 << 16, as in the shared kernels: a shift of the sample word
+// instead would be one more VALU instruction in every odd step of the LaneMajor loop, the register costs N VGPRs where these kernels
+// are far from any occupancy step (profiles/NOTES.md, "Biquad i16 by lane").  FrameMajor never takes the odd step: b0hi is dead there.
+template <int N, bool CLAMP>
+__device__ __forceinline__ void load_sections(Params<N> &prm, const int16_t *coef, size_t lanes, size_t lane, int frac)
+{
+    constexpr int CV = CLAMP ? 8 : 5;
+    auto at = [&](int k, int v) { return uint32_t(uint16_t(coef[size_t(k * CV + v) * lanes + lane])); };
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        Sec &d = prm.sec[k];
+        d.b0lo = at(k, 0), d.b0hi = d.b0lo << 16;
+        d.b12 = pack16(at(k, 1), at(k, 2));
+        d.a12 = pack16(at(k, 3), at(k, 4));
+        d.frac = frac;  // one F for the bank: wave-uniform, it stays in an SGPR
+        d.u = d.mn = d.mx = 0;
+        if (CLAMP) d.u = lo16(at(k, 5)), d.mn = lo16(at(k, 6)), d.mx = lo16(at(k, 7));
+    }
+}
+
+template <int N, bool CLAMP, int U>
+__global__ __launch_bounds__(256) void biquad_i16_bylane_frame_major(const int16_t *coef, const int frac, uint32_t *st, const int16_t *x, int16_t *y,
+                                                                     const size_t lanes, const size_t frames, const size_t xl, const size_t yl)
+{
+    const size_t lane = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (lane >= lanes) return;  // before any plane is read
+
+    Params<N> prm;
+    load_sections<N, CLAMP>(prm, coef, lanes, lane, frac);
+    Core<N, CLAMP> p;
+    p.load(st, lanes, lane);
+    const uint32_t voff = uint32_t(lane) * 2u;
+
+    subword::window_walk<U>(
+        frames, [&](size_t f) -> uint32_t { return global_ld<uint16_t, true>(x + f * xl, voff); },
+        [&](uint32_t v, size_t f) { global_st<uint16_t, true>(y + f * yl, voff, uint16_t(p.template step<false>(prm, v))); });
+    p.store(st, lanes, lane);
+}
+
+// biquad_i16_lane_major with the sections in registers.  The body is that kernel's, line for line, and is spelled out a second time on
+// purpose: the shared-coefficient kernel is what this one is measured against (profiles/NOTES.md, "Biquad i16 by lane"), and routing
+// both through one inlined body was tried and changed ITS code — other register allocation, other s_waitcnt placement, 30-80
+// instructions fewer of about 8000 —, which would have needed a measurement of its own against the kernel as it stood.
+template <int N, bool CLAMP>
+__global__ __launch_bounds__(kWave) void biquad_i16_bylane_lane_major(const int16_t *coef, const int frac, uint32_t *st, const int16_t *x, int16_t *y,
+                                                                      const size_t lanes, const size_t frames, const size_t xl, const size_t yl,
+                                                                      const int grid4)
+{
+    constexpr int TW = kLmTW, TS = kLmTS;
+    static_assert(TW == kWave, "a load instruction covers one row of the tile");
+    __shared__ uint32_t tile[kWave][TW + 1];
+
+    const subword::WaveRows w(lanes);
+    const int lid = w.lid;
+    const size_t lane0 = w.lane0, lane = w.lane, nrows = w.nrows;
+    const bool active = w.active;
+
+    Params<N> prm = {};  // a thread of the ragged last wave has no lane: it moves rows and never steps
+    Core<N, CLAMP> p;
+    if (active) {  // the predicate of the state load: nothing is read past the last lane of a plane
+        load_sections<N, CLAMP>(prm, coef, lanes, lane, frac);
+        p.load(st, lanes, lane);
+    }
+
+    uint32_t stage[kWave];
+    auto fetch = [&](size_t t0) {
+        const size_t ns = frames - t0 < size_t(TS) ? frames - t0 : size_t(TS);
+        if (grid4 && ns == size_t(TS)) {
+            subword::fetch_dwords(stage, w, x, xl, t0, true);  // a whole tile: no column predicate
+        } else {  // this family's own: rows off the 4-byte grid and the partial tile, a dword from two 16-bit loads
+            const bool h0 = size_t(2 * lid) < ns, h1 = size_t(2 * lid + 1) < ns;
+#pragma unroll
+            for (int r = 0; r < kWave; r++) {
+                uint32_t w = 0;
+                if (size_t(r) < nrows) {
+                    const int16_t *row = x + (lane0 + r) * xl + t0;
+                    if (grid4 && h1) {
+                        w = global_ld<uint32_t, true>(row, uint32_t(lid) * 4u);
+                    } else {
+                        if (h0) w = global_ld<uint16_t, true>(row, uint32_t(lid) * 4u);
+                        if (h1) w |= uint32_t(global_ld<uint16_t, true>(row, uint32_t(lid) * 4u + 2u)) << 16;
+                    }
+                }
+                stage[r] = w;
+            }
+        }
+    };
+
+    fetch(0);
+    for (size_t t0 = 0; t0 < frames; t0 += TS) {
+        const size_t ns = frames - t0 < size_t(TS) ? frames - t0 : size_t(TS);
+        subword::deposit(tile, stage, lid);
+        lds_wave_sync();
+        if (t0 + TS < frames) fetch(t0 + TS);
+
+        if (active) {
+            if (ns == size_t(TS)) {
+#pragma unroll 8
+                for (int j = 0; j < TW; j++) {
+                    const uint32_t w = tile[lid][j];
+                    const uint32_t y0 = p.template step<false>(prm, w);
+                    const uint32_t y1 = p.template step<true>(prm, w);
+                    tile[lid][j] = pack16(y0, y1);
+                }
+            } else {
+                for (size_t j = 0; 2 * j < ns; j++) {
+                    const uint32_t w = tile[lid][j];
+                    const uint32_t y0 = p.template step<false>(prm, w);
+                    const uint32_t y1 = 2 * j + 1 < ns ? p.template step<true>(prm, w) : 0u;
+                    tile[lid][j] = pack16(y0, y1);
+                }
+            }
+        }
+        lds_wave_sync();
+        if (grid4 && ns == size_t(TS)) {
+#pragma unroll 8
+            for (int r = 0; r < kWave; r++)
+                if (size_t(r) < nrows) global_st<uint32_t, true>(y + (lane0 + r) * yl + t0, uint32_t(lid) * 4u, tile[r][lid]);
+        } else {
+            const bool h0 = size_t(2 * lid) < ns, h1 = size_t(2 * lid + 1) < ns;
+            for (size_t r = 0; r < nrows; r++) {
+                int16_t *row = y + (lane0 + r) * yl + t0;
+                const uint32_t w = tile[r][lid];
+                if (grid4 && h1) {
+                    global_st<uint32_t, true>(row, uint32_t(lid) * 4u, w);
+                } else {
+                    if (h0) global_st<uint16_t, true>(row, uint32_t(lid) * 4u, uint16_t(w));
+                    if (h1) global_st<uint16_t, true>(row, uint32_t(lid) * 4u + 2u, uint16_t(w >> 16));
+                }
+            }
+        }
+        lds_wave_sync();
+    }
+    if (active) p.store(st, lanes, lane);
+}
+
 
 }  // namespace bq16
 }  // namespace idsp

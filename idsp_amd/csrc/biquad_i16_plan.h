@@ -56,5 +56,22 @@ inline Plan plan_biquad_i16(bool lane_major, size_t lanes, uintptr_t x, uintptr_
     return Plan{kFmPlain, unsigned((lanes + block - 1) / block), block, "biquad_i16_frame_major"};
 }
 
+// idsp_biquad_i16_df1_bylane / _df1_clamp_bylane (biquad_i16_bylane.hip): the same form on the same grid — where a section's
+// coefficients come from changes nothing about how rows move —, on kernels of their own, which idsp_last_kernel() tells apart
+inline const char *bylane_name(Form form)
+{
+    switch (form) {
+    case kLmDwordRuns: return "biquad_i16_bylane_lane_major[dword runs]";
+    case kLmHalfRuns: return "biquad_i16_bylane_lane_major[half runs]";
+    default: return "biquad_i16_bylane_frame_major";
+    }
+}
+inline Plan plan_biquad_i16_bylane(bool lane_major, size_t lanes, uintptr_t x, uintptr_t y, size_t xl, size_t yl, const Switches &sw = {})
+{
+    Plan pl = plan_biquad_i16(lane_major, lanes, x, y, xl, yl, sw);
+    pl.name = bylane_name(pl.form);
+    return pl;
+}
+
 }  // namespace bq16
 }  // namespace idsp

@@ -30,6 +30,7 @@ own:
                                                           LockinLo(...).process_accu(x, accu, y, batch_log2, harmonic)
     Dsm<K> (u32 -> i8)                   (dsm.rs:22-57)  Dsm(K).lanes(N)   y is torch.int8
     Biquad<Q16<F>> / BiquadClamp<Q16<F>, i16> (iir/biquad.rs:366-404) BiquadQ16(ba, frac=F[, u, min, max]).lanes(N)   x, y are torch.int16
+    ByLane<[Biquad<Q16<F>>; N]> / ..Clamp..   (compose.rs:363-390)    BiquadQ16ByLane([c0, c1, ..]), BiquadQ16ByLane.from_sos(sos, F)
     cossin(phase)                        (cossin.rs:14)  cossin(phases)
     atan2(y, x) / Complex::arg           (atan2.rs:66)   atan2(xy)
     cordic::{cos_sin, sqrt_atan2, ...}   (cordic.rs:80-107) cordic_cos_sin(xy, z), cordic_sqrt_atan2(xy, z), ...
@@ -54,7 +55,7 @@ __all__ = [
     "FrameMajor", "LaneMajor", "View", "ViewMut", "Biquad", "BiquadClamp", "Cascade",
     "DirectForm1", "DirectForm2Transposed", "DirectForm1Wide", "DirectForm1Dither", "DirectForm",
     "Split", "Lanes", "ByLane", "HbfDecCascade", "HbfIntCascade", "FirSym", "Cic", "Normal", "Wdf", "HBF_TAPS", "HBF_TAPS_98",
-    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "Sweep", "SweepOsc", "FmDisc", "PLL", "RPLLConfig", "RPLLLanes", "accu_lo", "Dsm", "DsmLanes", "BiquadQ16", "BiquadQ16Lanes", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
+    "Lowpass", "Lockin", "LockinLo", "Accu", "Dds", "Sweep", "SweepOsc", "FmDisc", "PLL", "RPLLConfig", "RPLLLanes", "accu_lo", "Dsm", "DsmLanes", "BiquadQ16", "BiquadQ16Lanes", "BiquadQ16ByLane", "Unwrapper", "ClampWrap", "PolyphaseBank", "overflowing_sub", "saturating_scale", "cossin", "atan2", "cordic_cos_sin", "cordic_sqrt_atan2", "cordic_cosh_sinh", "cordic_sqrt_atanh2", "cordic_mul", "cordic_div",
     "cordic_circular_gain", "cordic_hyperbolic_gain", "sos", "sos_clamp_wide", "IdspError",
 ]
 
@@ -1312,6 +1313,79 @@ class BiquadQ16Lanes(_LaneOp):
             return  # empty tensors have no data pointer
         call("biquad_i16_df1_clamp" if self.clamp else "biquad_i16_df1", self._cfg, self._n, C.c_void_p(self.state.data_ptr()),
              C.c_void_p(x.data_ptr()), 0, C.c_void_p(y.data_ptr()), 0, self.n_lanes, frames, layout, _stream_ptr(x))
+
+
+class BiquadQ16ByLane(_LaneOp):
+    """`Split<ByLane<[C; N]>, [S; N]>` (dsp-process/src/compose.rs:363-390) with C = `Biquad<Q16<F>>` or `BiquadClamp<Q16<F>, i16>` and
+    S = `DirectForm1<i16>`: lane i is filtered by configuration i on state i (idsp_biquad_i16_df1_bylane / _df1_clamp_bylane).
+    `configs[i]` is a BiquadQ16 or a list of them (serial slice, compose.rs:43-77); all lanes share the section count, plain or clamped,
+    and one F.  The coefficients live on the GPU as lane-contiguous planes, `.coef` [sections, 5 or 8, lanes] int16 ({b0, b1, b2, a1,
+    a2[, u, min, max]}), and may be rewritten between calls, one lane at a time with `set_lane`.  x, y, `.state` and the dense-tensor
+    rule are those of BiquadQ16Lanes."""
+
+    dtype_in = dtype_out = torch.int16
+
+    def __init__(self, configs: Sequence, device="cuda"):
+        rows = [list(c) if isinstance(c, (list, tuple)) else [c] for c in configs]
+        if torch.device(device).type != "cuda":
+            raise ValueError("idsp_amd runs on the GPU only")
+        if not rows or not rows[0]:
+            raise ValueError("BiquadQ16ByLane needs at least one lane and one section")
+        first = rows[0][0]
+        if not isinstance(first, BiquadQ16):
+            raise ValueError("configs hold BiquadQ16")
+        if len(rows[0]) > _abi.MAX_SECTIONS:
+            raise ValueError(f"at most {_abi.MAX_SECTIONS} sections")
+        coef = torch.stack([self._planes(r, len(rows[0]), first.clamp, first.frac) for r in rows], dim=2)
+        self._adopt(coef, first.frac, first.clamp, device)
+
+    def _adopt(self, coef: torch.Tensor, frac: int, clamp: bool, device):
+        self._n, self.frac, self.clamp = coef.shape[0], frac, clamp
+        super().__init__(coef.shape[2], 4 * self._n, device)
+        self.coef = coef.contiguous().to(self.device)
+
+    @staticmethod
+    def _planes(row, n: int, clamp: bool, frac: int) -> torch.Tensor:
+        """one lane's sections -> [n, 5 or 8] int16 on the host"""
+        if len(row) != n:
+            raise ValueError("every lane needs the same number of sections")
+        if any(not isinstance(s, BiquadQ16) or s.clamp != clamp or s.frac != frac for s in row):
+            raise ValueError("all lanes of a BiquadQ16ByLane share plain or clamped sections and one frac")
+        return torch.tensor([s.ba + ([s.u, s.min, s.max] if clamp else []) for s in row], dtype=torch.int16)
+
+    @classmethod
+    def from_sos(cls, sos, frac: int, clamp: bool = False, device="cuda") -> "BiquadQ16ByLane":
+        """sos[lanes][n][6], each `[b0, b1, b2, a0, a1, a2]` quantised as BiquadQ16.from_sos does (idsp_biquad_i16_bank_from_sos); with
+        `clamp` the planes also hold `BiquadClamp::default`'s u = 0, min = i16::MIN, max = i16::MAX, for the caller to overwrite"""
+        if torch.device(device).type != "cuda":
+            raise ValueError("idsp_amd runs on the GPU only")
+        if isinstance(frac, bool) or not isinstance(frac, int) or not 0 <= frac <= 31:
+            raise ValueError("frac must be an integer in 0..=31")
+        t = torch.as_tensor(sos, dtype=torch.float64).contiguous()
+        if t.dim() != 3 or t.shape[2] != 6 or not t.shape[0] or not 1 <= t.shape[1] <= _abi.MAX_SECTIONS:
+            raise ValueError(f"sos is [lanes][n][6] with at least one lane and 1..{_abi.MAX_SECTIONS} sections")
+        lanes, n, cv = t.shape[0], t.shape[1], 8 if clamp else 5
+        load()
+        coef = torch.empty((n, cv, lanes), dtype=torch.int16)
+        call("biquad_i16_bank_from_sos", C.c_void_p(t.data_ptr()), lanes, n, frac, cv, C.c_void_p(coef.data_ptr()))
+        self = cls.__new__(cls)
+        self._adopt(coef, frac, bool(clamp), device)
+        return self
+
+    def set_lane(self, lane: int, config):
+        """Replace the configuration of one lane (its state is kept, like assigning `by_lane.0[i]`)."""
+        if not 0 <= lane < self.n_lanes:
+            raise ValueError("lane out of range")
+        row = list(config) if isinstance(config, (list, tuple)) else [config]
+        self.coef[:, :, lane] = self._planes(row, self._n, self.clamp, self.frac).to(self.device)
+
+    def _run(self, x, y, frames, layout):
+        if x.device != self.state.device or y.device != self.state.device:
+            raise ValueError("x and y must be on the device of the state")
+        if frames == 0:
+            return  # empty tensors have no data pointer
+        call("biquad_i16_df1_clamp_bylane" if self.clamp else "biquad_i16_df1_bylane", C.c_void_p(self.coef.data_ptr()), self.frac, self._n,
+             C.c_void_p(self.state.data_ptr()), C.c_void_p(x.data_ptr()), 0, C.c_void_p(y.data_ptr()), 0, self.n_lanes, frames, layout, _stream_ptr(x))
 
 
 class PolyphaseBank(_LaneOp):

@@ -288,6 +288,29 @@ int idsp_biquad_i16_df1(const idsp_biquad_i16 *cfg, size_t n, void *state, const
 int idsp_biquad_i16_df1_clamp(const idsp_biquad_clamp_i16 *cfg, size_t n, void *state, const int16_t *x, size_t x_pitch,
                               int16_t *y, size_t y_pitch, size_t lanes, size_t frames, int layout, void *stream);
 
+/*
+ * Per-lane coefficient banks: `ByLane<[Biquad<Q16<F>>; N]>` / `ByLane<[BiquadClamp<Q16<F>, i16>; N]>` (dsp-process/src/compose.rs:363-390),
+ * each configuration a slice of n sections (compose.rs:43-77).  Lane l is filtered by configuration l on state l; the arithmetic,
+ * the state layout, the pitches, the alignment and in-place rules, n == 0, the passes of up to four sections and the kernel forms are
+ * those of idsp_biquad_i16_df1 / _df1_clamp above.  Only the source of the coefficients changes.
+ * coef: a DEVICE array of int16_t in lane-contiguous planes, the convention of idsp_biquad_i32_df1_bylane: value v of section k of
+ * lane l is coef[(k*CV + v)*lanes + l], CV = 5 { b0, b1, b2, a1, a2 } (a1, a2 as used), CV = 8 { .., u, min, max } for the clamp
+ * entry; n*CV*lanes elements.  Any 2-byte-aligned address: with an odd lane count every other plane is off the 4-byte grid anyway.
+ * Read once per pass, before the first frame; read-only for the call.  Overlap of coef with y or state is NOT checked.
+ * frac: the one F of `Q16<F>`, 0..31, shared by all lanes and sections (a const generic in the reference).
+ * IDSP_EINVAL in addition, with nothing written: NULL coef with n > 0 and lanes > 0, an odd coef address.
+ * idsp_last_kernel(): "biquad_i16_bylane_frame_major", "biquad_i16_bylane_lane_major[dword runs]" / "[half runs]".
+ */
+int idsp_biquad_i16_df1_bylane(const int16_t *coef, int frac, size_t n, void *state, const int16_t *x, size_t x_pitch,
+                               int16_t *y, size_t y_pitch, size_t lanes, size_t frames, int layout, void *stream);
+int idsp_biquad_i16_df1_clamp_bylane(const int16_t *coef, int frac, size_t n, void *state, const int16_t *x, size_t x_pitch,
+                                     int16_t *y, size_t y_pitch, size_t lanes, size_t frames, int layout, void *stream);
+/* sos[lanes][n][6] -> the planes above, on the HOST: each [b0,b1,b2,a0,a1,a2] quantised as idsp_biquad_i16_from_sos does; with
+ * cv == 8 also u = 0, min = INT16_MIN, max = INT16_MAX (`BiquadClamp::default`, biquad.rs:159-171) for the caller to overwrite.
+ * coef: n*cv*lanes elements of host memory.  IDSP_EINVAL: frac outside 0..31, cv neither 5 nor 8, n > IDSP_MAX_SECTIONS, NULL sos
+ * or coef with lanes > 0 and n > 0. */
+int idsp_biquad_i16_bank_from_sos(const double *sos, size_t lanes, size_t n, int frac, size_t cv, int16_t *coef);
+
 /* ------------------------------------------------------------------------ */
 /* iir::Biquad — f32                                                        */
 /* ------------------------------------------------------------------------ */

@@ -1461,4 +1461,100 @@ private:
     DeviceBuffer<uint32_t> state_;
 };
 
+/// `Split<ByLane<[C; lanes]>, [S; lanes]>` (dsp-process/src/compose.rs:363-390) with C = `Biquad<Q16<F>>` (Cfg = idsp_biquad_i16) or
+/// `BiquadClamp<Q16<F>, i16>` (Cfg = idsp_biquad_clamp_i16) and S = `DirectForm1<i16>`: lane i is filtered by configuration i on
+/// state i (idsp_biquad_i16_df1_bylane / _df1_clamp_bylane).  `configs[i]` is the serial slice of sections of lane i; every lane has
+/// the same number of sections and every section the same frac (the one F of the bank).  The coefficients are kept on the GPU as
+/// lane-contiguous i16 planes.
+template <class Cfg>
+class BiquadI16ByLane {
+    static_assert(std::is_same<Cfg, idsp_biquad_i16>::value || std::is_same<Cfg, idsp_biquad_clamp_i16>::value, "Cfg: idsp_biquad_i16 or idsp_biquad_clamp_i16");
+
+public:
+    static constexpr size_t cv = std::is_same<Cfg, idsp_biquad_i16>::value ? 5 : 8;  ///< values per section and lane
+    /// the planes of `configs` on the host, value v of section k of lane l at [(k * cv + v) * lanes + l]; checks what the class requires
+    static std::vector<int16_t> planes(const std::vector<std::vector<Cfg>> &configs)
+    {
+        const size_t lanes = configs.size(), n = lanes ? configs[0].size() : 0;
+        require(lanes && n, "BiquadI16ByLane needs at least one lane and one section");
+        require(n <= IDSP_MAX_SECTIONS, "at most IDSP_MAX_SECTIONS sections");
+        const int frac = configs[0][0].frac;
+        require(frac >= 0 && frac <= 31, "frac must be in 0..=31");
+        std::vector<int16_t> host(n * cv * lanes);
+        for (size_t l = 0; l < lanes; l++) {
+            require(configs[l].size() == n, "every lane needs the same number of sections");
+            for (size_t k = 0; k < n; k++) {
+                const Cfg &c = configs[l][k];
+                require(c.frac == frac, "all lanes and sections of a bank share one frac");
+                for (size_t v = 0; v < 5; v++) host[(k * cv + v) * lanes + l] = c.ba[v];
+                if constexpr (cv == 8) {
+                    host[(k * cv + 5) * lanes + l] = c.u;
+                    host[(k * cv + 6) * lanes + l] = c.min;
+                    host[(k * cv + 7) * lanes + l] = c.max;
+                }
+            }
+        }
+        return host;
+    }
+    explicit BiquadI16ByLane(const std::vector<std::vector<Cfg>> &configs, void *stream = nullptr)
+        : host_(planes(configs)), lanes_(configs.size()), sections_(configs[0].size()), frac_(configs[0][0].frac), stream_(stream),
+          state_(idsp_biquad_i16_state_words(sections_) * lanes_), coef_(host_)
+    {
+    }
+    size_t lanes() const { return lanes_; }
+    size_t sections() const { return sections_; }
+    int frac() const { return frac_; }
+    DeviceBuffer<uint32_t> &state() { return state_; }
+    DeviceBuffer<int16_t> &coefficients() { return coef_; }
+    /// back to `Default::default()` in every lane
+    void reset() { check(idsp_device_memset(state_.data(), 0, state_.len() * sizeof(uint32_t), stream_)); }
+    /// replace the configuration of one lane; its state is kept (assigning `by_lane.0[lane]`)
+    void set_lane(size_t lane, const std::vector<Cfg> &config)
+    {
+        require(lane < lanes_, "lane out of range");
+        require(config.size() == sections_, "every lane needs the same number of sections");
+        for (const Cfg &c : config) require(c.frac == frac_, "all lanes and sections of a bank share one frac");
+        const std::vector<int16_t> one = planes({config});
+        for (size_t i = 0; i < sections_ * cv; i++) host_[i * lanes_ + lane] = one[i];
+        coef_.upload(host_);
+    }
+    /// pitches, alignment and in place: as `BiquadI16Lanes::process_view`
+    template <class Layout>
+    void process_view(View<int16_t, Layout> x, ViewMut<int16_t, Layout> y, size_t x_pitch = 0, size_t y_pitch = 0)
+    {
+        require(x.frames == y.frames && x.lanes == lanes_ && y.lanes == lanes_, "view shape mismatch");
+        const size_t row = Layout::value == IDSP_LANE_MAJOR ? x.frames : lanes_;
+        require((!x_pitch || x_pitch >= row) && (!y_pitch || y_pitch >= row), "pitch shorter than a row");
+        if (x.frames == 0) return;
+        if constexpr (cv == 5)
+            check(idsp_biquad_i16_df1_bylane(coef_.data(), frac_, sections_, state_.data(), x.flat, x_pitch, y.flat, y_pitch, lanes_, x.frames, Layout::value, stream_));
+        else
+            check(idsp_biquad_i16_df1_clamp_bylane(coef_.data(), frac_, sections_, state_.data(), x.flat, x_pitch, y.flat, y_pitch, lanes_, x.frames, Layout::value, stream_));
+    }
+    /// `Process::block` over `&[[i16; N]]`: FrameMajor
+    void block(View<int16_t, FrameMajor> x, ViewMut<int16_t, FrameMajor> y, size_t x_pitch = 0, size_t y_pitch = 0) { process_view(x, y, x_pitch, y_pitch); }
+    template <class Layout>
+    void inplace_view(ViewMut<int16_t, Layout> xy, size_t pitch = 0)
+    {
+        process_view(View<int16_t, Layout>{xy.flat, xy.frames, xy.lanes}, xy, pitch, pitch);
+    }
+
+private:
+    std::vector<int16_t> host_;  // the planes as uploaded: set_lane edits and uploads again
+    size_t lanes_, sections_;
+    int frac_;
+    void *stream_;
+    DeviceBuffer<uint32_t> state_;
+    DeviceBuffer<int16_t> coef_;
+};
+
+/// sos[lanes][n][6] -> the host planes of a bank (idsp_biquad_i16_bank_from_sos); cv = 8 adds `BiquadClamp::default`'s u, min, max
+inline std::vector<int16_t> biquad_i16_bank_from_sos(const std::vector<double> &sos, size_t lanes, size_t n, int frac, size_t cv = 5)
+{
+    require(sos.size() == lanes * n * 6, "sos is [lanes][n][6]");
+    std::vector<int16_t> coef(n * (cv == 8 ? 8 : 5) * lanes);
+    check(idsp_biquad_i16_bank_from_sos(sos.data(), lanes, n, frac, cv, coef.data()));
+    return coef;
+}
+
 }  // namespace idsp_hip
