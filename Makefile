@@ -71,9 +71,10 @@ build/test_coeff: tests/cpp/test_coeff.cpp include/idsp_hip.hpp include/idsp_hip
 	@mkdir -p build
 	g++ -std=c++17 -O1 -Wall -Iinclude tests/cpp/test_coeff.cpp -Lidsp_amd/lib -lidsp_hip -Wl,-rpath,'$$ORIGIN/../idsp_amd/lib' -o $@
 
-# the dispatch of launch_stream, of the lock-in entries, of the half-band and Cic entries and of the FM discriminator and DDS entries as a host
-# program (tests/test_stream_plan.py, tests/test_lockin_plan.py, tests/test_resample_plan.py, tests/test_fm_disc_plan.py): plain g++, neither HIP nor the library
-build/stream_plan_cli: tests/cpp/stream_plan_cli.cpp $(CSRC)/stream_plan.h $(CSRC)/lockin_plan.h $(CSRC)/resample_plan.h $(CSRC)/readout_plan.h $(CSRC)/dispatch_thresholds.h include/idsp_hip.h
+# the dispatch of launch_stream, of the lock-in entries, of the half-band and Cic entries, of the FM discriminator and DDS entries and the passes of the
+# biquad chains as a host program (tests/test_stream_plan.py, tests/test_lockin_plan.py, tests/test_resample_plan.py, tests/test_fm_disc_plan.py,
+# tests/test_biquad_pass_plan.py): plain g++, neither HIP nor the library
+build/stream_plan_cli: tests/cpp/stream_plan_cli.cpp $(CSRC)/stream_plan.h $(CSRC)/lockin_plan.h $(CSRC)/resample_plan.h $(CSRC)/readout_plan.h $(CSRC)/biquad_pass_plan.h $(CSRC)/dispatch_thresholds.h include/idsp_hip.h
 	@mkdir -p build
 	g++ -std=c++17 -O1 -Wall -Wextra -Iinclude tests/cpp/stream_plan_cli.cpp -o $@
 

@@ -1,6 +1,6 @@
 // biquad_bylane_f.hip — C-ABI entry points (include/idsp_hip.h) of the per-lane-coefficient f32 biquads (f64: biquad_bylane_f64.hip)
-// (`ByLane<[Biquad<f32>; N]>`, dsp-process/src/compose.rs:363-390); device code in biquad_sections.h.
-#include "biquad_sections.h"
+// (`ByLane<[Biquad<f32>; N]>`, dsp-process/src/compose.rs:363-390); device code in biquad_sections.h, host side in biquad_host.h.
+#include "biquad_host.h"
 
 using namespace idsp;
 using namespace idsp::bq;

@@ -1,6 +1,6 @@
 // biquad_bylane_i32_wide.hip — (second half of biquad_bylane_i32.hip: the clamped dither and the wide sections) C-ABI entry points (include/idsp_hip.h) of the per-lane-coefficient i32 biquads
-// (`ByLane<[Biquad<Q32<F>>; N]>`, dsp-process/src/compose.rs:363-390); device code in biquad_sections.h.
-#include "biquad_sections.h"
+// (`ByLane<[Biquad<Q32<F>>; N]>`, dsp-process/src/compose.rs:363-390); device code in biquad_sections.h, host side in biquad_host.h.
+#include "biquad_host.h"
 
 using namespace idsp;
 using namespace idsp::bq;

@@ -1,5 +1,5 @@
-// biquad_f32_df1.hip — C-ABI entry points (include/idsp_hip.h) of this family; device code in biquad_sections.h.
-#include "biquad_sections.h"
+// biquad_f32_df1.hip — C-ABI entry points (include/idsp_hip.h) of this family; device code in biquad_sections.h, host side in biquad_host.h.
+#include "biquad_host.h"
 
 using namespace idsp;
 using namespace idsp::bq;
@@ -9,17 +9,17 @@ extern "C" {
 int idsp_biquad_f32_df1(const idsp_biquad_f32 *cfg, size_t n, void *state, const float *x, float *y,
                         size_t lanes, size_t frames, int layout, void *stream)
 {
-    return entry_f32<Df1F32<false>, idsp_biquad_f32, FillF32>(cfg, n, state, x, y, lanes, frames, layout, stream);
+    return entry_chain<Df1F32<false>, idsp_biquad_f32, Fill<idsp_biquad_f32>>(cfg, n, state, x, y, lanes, frames, layout, stream);
 }
 
 int idsp_biquad_f32_df1_clamp(const idsp_biquad_clamp_f32 *cfg, size_t n, void *state, const float *x, float *y,
                               size_t lanes, size_t frames, int layout, void *stream)
 {
-    return entry_f32<Df1F32<true>, idsp_biquad_clamp_f32, FillClampF32>(cfg, n, state, x, y, lanes, frames, layout, stream);
+    return entry_chain<Df1F32<true>, idsp_biquad_clamp_f32, FillClamp<idsp_biquad_clamp_f32>>(cfg, n, state, x, y, lanes, frames, layout, stream);
 }
 
 // explicit row pitches (include/idsp_hip.h, "_pitch" entries)
-IDSP_PITCH_TWIN(idsp_biquad_f32_df1, idsp_biquad_f32, float, entry_f32, Df1F32<false>, idsp_biquad_f32, FillF32)
-IDSP_PITCH_TWIN(idsp_biquad_f32_df1_clamp, idsp_biquad_clamp_f32, float, entry_f32, Df1F32<true>, idsp_biquad_clamp_f32, FillClampF32)
+IDSP_PITCH_TWIN(idsp_biquad_f32_df1, idsp_biquad_f32, float, entry_chain, Df1F32<false>, idsp_biquad_f32, Fill<idsp_biquad_f32>)
+IDSP_PITCH_TWIN(idsp_biquad_f32_df1_clamp, idsp_biquad_clamp_f32, float, entry_chain, Df1F32<true>, idsp_biquad_clamp_f32, FillClamp<idsp_biquad_clamp_f32>)
 
 }  // extern "C"

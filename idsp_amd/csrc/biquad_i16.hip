@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "biquad_i16_kernels.h"
+#include "biquad_pass_plan.h"
 
 namespace idsp {
 namespace {
@@ -69,12 +70,12 @@ int entry(const Cfg *cfg, size_t n, void *state, const int16_t *x, size_t x_pitc
         if (x != y) IDSP_HIP_TRY(hipMemcpy2DAsync(y, yl * 2, x, xl * 2, row * 2, rows, hipMemcpyDeviceToDevice, s));
         return IDSP_OK;
     }
-    // passes of <= kMaxChain sections: the first reads x, later ones run in place on y — literally the reference's slice composition
+    // the passes of biquad_pass_plan.h (never two waves): the first reads x, later ones run in place on y — literally the reference's slice composition
     uint32_t *st = static_cast<uint32_t *>(state);
     const int16_t *src = x;
     size_t sl = xl;
     for (size_t done = 0; done < n;) {
-        const size_t m = n - done < size_t(kMaxChain) ? n - done : size_t(kMaxChain);
+        const int m = next_pass(i16_rules(), n - done, lanes, layout, StreamSwitches{}).na;
         int rc;
         switch (m) {
         case 1: rc = run_pass<1, CLAMP>(cfg, done, st, src, sl, y, yl, lanes, frames, layout, s); break;
@@ -83,7 +84,7 @@ int entry(const Cfg *cfg, size_t n, void *state, const int16_t *x, size_t x_pitc
         default: rc = run_pass<4, CLAMP>(cfg, done, st, src, sl, y, yl, lanes, frames, layout, s); break;
         }
         if (rc) return rc;
-        done += m;
+        done += size_t(m);
         src = y, sl = yl;
     }
     return IDSP_OK;

@@ -3,6 +3,7 @@
 // checks, the passes and the dispatch are those of biquad_i16.hip; a pass takes its planes from `coef` where that one takes its
 // sections from `cfg`.  (A unit of its own: its 16 kernels compile beside the 16 of biquad_i16.hip under `make -j`.)
 #include "biquad_i16_kernels.h"
+#include "biquad_pass_plan.h"
 
 namespace idsp {
 namespace {
@@ -48,12 +49,12 @@ int entry(const int16_t *coef, int frac, size_t n, void *state, const int16_t *x
         if (x != y) IDSP_HIP_TRY(hipMemcpy2DAsync(y, yl * 2, x, xl * 2, row * 2, rows, hipMemcpyDeviceToDevice, s));
         return IDSP_OK;
     }
-    // passes of <= kMaxChain sections: the first reads x, later ones run in place on y (biquad_i16.hip)
+    // the passes of biquad_pass_plan.h (never two waves): the first reads x, later ones run in place on y — (biquad_i16.hip)
     uint32_t *st = static_cast<uint32_t *>(state);
     const int16_t *src = x;
     size_t sl = xl;
     for (size_t done = 0; done < n;) {
-        const size_t m = n - done < size_t(kMaxChain) ? n - done : size_t(kMaxChain);
+        const int m = next_pass(i16_rules(), n - done, lanes, layout, StreamSwitches{}).na;
         int rc;
         switch (m) {
         case 1: rc = run_pass<1, CLAMP>(coef, frac, done, st, src, sl, y, yl, lanes, frames, layout, s); break;
@@ -62,7 +63,7 @@ int entry(const int16_t *coef, int frac, size_t n, void *state, const int16_t *x
         default: rc = run_pass<4, CLAMP>(coef, frac, done, st, src, sl, y, yl, lanes, frames, layout, s); break;
         }
         if (rc) return rc;
-        done += m;
+        done += size_t(m);
         src = y, sl = yl;
     }
     return IDSP_OK;

@@ -19,7 +19,7 @@ namespace idsp {
 namespace bq16 {
 
 constexpr int kWave = 64;
-constexpr int kMaxChain = 4;  // sections fused per launch; longer chains run in passes, in place on y
+// (sections fused per launch, bq16::kMaxChain: biquad_pass_plan.h)
 // Threads per FRAME_MAJOR workgroup.  One wave, so that few waves still spread over all CUs, until the waves fill every SIMD of a 256-CU
 // part once; from there four.  Measured at 4096 frames with 64 / 256: 16384 lanes 0.158 / 0.162 ms, 65536 lanes 0.208 / 0.199
 // (profiles/NOTES.md, "Biquad i16"); nothing between or beyond was measured.

@@ -7,7 +7,8 @@
 // reference's stage-major slice composition (dsp-process/src/compose.rs:43-77)
 // because every section is a causal function of its own input sequence.
 // The extern "C" entry points live in biquad_*.hip (one translation unit per
-// family so the many template instances compile in parallel).
+// family so the many template instances compile in parallel); their host side —
+// checks, the passes of a long chain, the launches — is biquad_host.h.
 //
 // Integer paths are bit-exact restatements of Rust release (wrapping)
 // arithmetic: i32 x i32 -> i64 products (v_mad_i64_i32), wrapping i64 sums,
@@ -16,15 +17,13 @@
 // (the library is compiled with -ffp-contract=off; f32 denormals enabled).
 #pragma once
 
+#include <limits>
 #include <type_traits>
 
 #include "lane_stream.h"
 
 namespace idsp {
 namespace bq {
-
-constexpr int kMaxChain = 4;    // sections fused per launch; longer chains run in passes
-constexpr int kMaxCascade = 8;  // Cascade<[Biquad; N]> shares delay lines: single launch
 
 __device__ __forceinline__ int64_t mulw(int32_t c, int32_t v) { return int64_t(c) * int64_t(v); }
 __device__ __forceinline__ int64_t wadd(int64_t a, int64_t b) { return int64_t(uint64_t(a) + uint64_t(b)); }
@@ -55,12 +54,70 @@ template <class S, int N>
 struct ChainParams {
     S sec[N];
 };
-// `fill` is one of the Fill* functors below
-template <class Fill, class S, int N>
-inline void fill_sections(const Fill &fill, S (&sec)[N])
+// Section k of a host config array (include/idsp_hip.h) into its POD.  `Fill` takes idsp_biquad_{i32,f32,f64} — no offset, no limits —,
+// `FillClamp` idsp_biquad_clamp_{i32,f32,f64}; `frac` where the config has one.
+template <class Cfg, class = void>
+struct HasFrac : std::false_type {};
+template <class Cfg>
+struct HasFrac<Cfg, std::void_t<decltype(Cfg::frac)>> : std::true_type {};
+template <class Cfg>
+struct Fill {
+    const Cfg *c;
+    template <class S>
+    void operator()(S &d, size_t k) const
+    {
+        using V = decltype(d.u);
+        using L = std::numeric_limits<V>;
+        for (int i = 0; i < 5; i++) d.ba[i] = c[k].ba[i];
+        if constexpr (HasFrac<Cfg>::value) d.frac = c[k].frac;
+        d.u = V(0);
+        d.mn = L::has_infinity ? -L::infinity() : L::lowest();
+        d.mx = L::has_infinity ? L::infinity() : L::max();
+    }
+};
+template <class Cfg>
+struct FillClamp {
+    const Cfg *c;
+    template <class S>
+    void operator()(S &d, size_t k) const
+    {
+        for (int i = 0; i < 5; i++) d.ba[i] = c[k].ba[i];
+        if constexpr (HasFrac<Cfg>::value) d.frac = c[k].frac;
+        d.u = c[k].u;
+        d.mn = c[k].min;
+        d.mx = c[k].max;
+    }
+};
+template <class Cfg>
+Fill(const Cfg *) -> Fill<Cfg>;
+template <class Cfg>
+FillClamp(const Cfg *) -> FillClamp<Cfg>;
+template <class CfgFill, class S, int N>
+inline void fill_sections(const CfgFill &fill, S (&sec)[N])
 {
     for (int k = 0; k < N; k++) fill(sec[k], size_t(k));
 }
+
+// What a section type that says nothing hands `Chain` / `ChainByLane` below; the section structs derive from it and shadow what they tune
+struct SecDefaults {
+    static constexpr int LDS_RING = 8;       // LDS-DMA ring depth of a one-section processor
+    static constexpr bool LDS_RUN = false;
+    // Section count up to which a chain of this section type runs faster on the LDS-DMA kernel than on the register-window
+    // kernel at the C2 shape, both at their worst output placement (tools/tune_lds.hip): i32 DF1 x3 0.77 vs 0.62, x4 0.61 vs
+    // 0.68; wide x2 0.73 vs 0.65; f32 DF1 / DF2T x2 0.75-0.77 vs 0.60-0.69, x3 0.70 vs 0.71, x4 0.54-0.57 vs 0.57-0.62;
+    // Normal x2 0.77-0.81 vs 0.66-0.70, x4 0.51 vs 0.53.
+    static constexpr int LDS_MAX_N = 0;      // f64 sections: 8-byte samples never take the LDS-DMA kernel
+    // largest number of sub-blocks per workgroup a single section is instantiated with on the sweep kernel: 16 (2^20 lanes in one sweep) for the
+    // biquad sections proper (Normal: 8)
+    static constexpr int SWEEP_LPT = 16;
+    // sections whose single-section processors run 8 / 16 blocks per workgroup of the sweep kernel on its two-barrier schedule (fm_sweep.h)
+    static constexpr bool SWEEP_BIG_TWO_BARRIER = false;
+    // sections whose full blocks the sweep kernel runs WITHOUT the `s_sleep` pacing although they are cheap: `Normal` f32 — and the clamped ones, which
+    // `Chain` adds (65536 lanes: f32 DF1 clamp 0.67 of the peak paced, 0.76 unpaced; f32 DF2T clamp 0.69 / 0.75; i32 DF1 clamp 0.73 / 0.75; Normal f32
+    // 0.73 / 0.75 — the unclamped ones 0.77-0.80 / 0.76)
+    static constexpr bool SWEEP_UNPACED = false;
+    static constexpr bool HAS_TILE = false;  // a `tile` member (Df1I32)
+};
 
 // The state of NS serial sections of W words each on one lock-in arm (lockin_generic.hip, lockin_waves_biquad.hip): words
 // `word0 + k W + w` of the lane's record, section-major
@@ -97,11 +154,10 @@ __device__ __forceinline__ int64_t sum5(const SecI32 &c, int32_t x0, int32_t x1,
 }
 
 template <bool CLAMP>
-struct Df1I32 {
+struct Df1I32 : SecDefaults {
     static constexpr bool kClamp = CLAMP;
     static constexpr bool SWEEP_BIG_TWO_BARRIER = !CLAMP;
     static constexpr int LDS_RING = CLAMP ? 4 : 7;   // tools/tune_lds.hip: best worst-case over four output placements (plain: 5, 6, 7 within 1.5 %)
-    static constexpr bool LDS_RUN = false;
     static constexpr int LDS_MAX_N = 3;     // serial sections up to which the LDS-DMA kernel beats the register window
     using T = int32_t;
     using Sec = SecI32;
@@ -167,10 +223,9 @@ struct Df1I32 {
 
 // src/iir/biquad.rs:511-538 (first-order error feedback)
 template <bool CLAMP>
-struct DitherI32 {
+struct DitherI32 : SecDefaults {
     static constexpr bool kClamp = CLAMP;
     static constexpr int LDS_RING = CLAMP ? 4 : 7;   // tools/tune_lds.hip: best worst-case over four output placements
-    static constexpr bool LDS_RUN = false;
     static constexpr int LDS_MAX_N = 2;     // serial sections up to which the LDS-DMA kernel beats the register window
     using T = int32_t;
     using Sec = SecI32;
@@ -195,7 +250,7 @@ struct DitherI32 {
 
 // src/iir/biquad.rs:456-480 (64-bit y state)
 template <bool CLAMP>
-struct WideI32 {
+struct WideI32 : SecDefaults {
     static constexpr bool kClamp = CLAMP;
     using T = int32_t;
     static constexpr int LDS_RING = CLAMP ? 4 : 5;   // tools/tune_lds.hip: best worst-case over four output placements
@@ -233,10 +288,9 @@ struct WideI32 {
 // ------------------------------------------------------------ f32 sections
 // src/iir/biquad.rs:366-383 (C = T = A = f32)
 template <bool CLAMP>
-struct Df1F32 {
+struct Df1F32 : SecDefaults {
     static constexpr bool kClamp = CLAMP;
     static constexpr int LDS_RING = CLAMP ? 4 : 5;   // tools/tune_lds.hip: best worst-case over four output placements
-    static constexpr bool LDS_RUN = false;
     static constexpr int LDS_MAX_N = 2;     // serial sections up to which the LDS-DMA kernel beats the register window
     using T = float;
     using Sec = SecF32;
@@ -260,11 +314,10 @@ struct Df1F32 {
 
 // src/iir/biquad.rs:418-440
 template <bool CLAMP>
-struct Df2tF32 {
+struct Df2tF32 : SecDefaults {
     static constexpr bool kClamp = CLAMP;
     static constexpr bool SWEEP_BIG_TWO_BARRIER = !CLAMP;
     static constexpr int LDS_RING = CLAMP ? 4 : 7;   // tools/tune_lds.hip: best worst-case over four output placements
-    static constexpr bool LDS_RUN = false;
     static constexpr int LDS_MAX_N = 2;     // serial sections up to which the LDS-DMA kernel beats the register window
     using T = float;
     using Sec = SecF32;
@@ -296,7 +349,7 @@ __device__ __forceinline__ void std_(uint32_t *s, int i, double v)
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 template <bool CLAMP>
-struct Df1F64 {
+struct Df1F64 : SecDefaults {
     static constexpr bool kClamp = CLAMP;
     using T = double;
     using Sec = SecF64;
@@ -319,7 +372,7 @@ struct Df1F64 {
 };
 
 template <bool CLAMP>
-struct Df2tF64 {
+struct Df2tF64 : SecDefaults {
     static constexpr bool kClamp = CLAMP;
     using T = double;
     using Sec = SecF64;
@@ -340,7 +393,7 @@ struct Df2tF64 {
 // ------------------------------------------------------------ normal form
 // `Normal<C>` x `DirectForm1<T>` (src/iir/normal.rs:37-58); ba = [b0, b1, b2, p.re, p.im], state words
 // {x0, x1, y0, y1}: y1' = (b0 x0 + b1 x1 + b2 x2 + re y1 + (-im) y0).as_(), y0' = (im y1 + re y0).as_().
-struct NormalI32 {
+struct NormalI32 : SecDefaults {
     static constexpr int SWEEP_LPT = 8;
     using T = int32_t;
     static constexpr int LDS_RING = 5;   // tools/tune_lds.hip: best worst-case over four output placements
@@ -367,7 +420,7 @@ struct NormalI32 {
         return y0;
     }
 };
-struct NormalF32 {
+struct NormalF32 : SecDefaults {
     static constexpr int SWEEP_LPT = 8;
     static constexpr bool SWEEP_BIG_TWO_BARRIER = true;
     static constexpr bool SWEEP_UNPACED = true;
@@ -395,7 +448,7 @@ struct NormalF32 {
         return y0;
     }
 };
-struct NormalF64 {
+struct NormalF64 : SecDefaults {
     using T = double;
     using Sec = SecF64;
     static constexpr bool kClamp = false;
@@ -419,65 +472,7 @@ struct NormalF64 {
 };
 
 // ------------------------------------------------------------ processors
-// LDS-DMA ring depth of a one-section processor: the section's LDS_RING if it names one, else 8
-template <class Sec, class = void>
-struct SecRing {
-    static constexpr int value = 8;
-};
-template <class Sec>
-struct SecRing<Sec, std::void_t<decltype(Sec::LDS_RING)>> {
-    static constexpr int value = Sec::LDS_RING;
-};
-
-template <class Sec, class = void>
-struct SecRun {
-    static constexpr bool value = false;
-};
-template <class Sec>
-struct SecRun<Sec, std::void_t<decltype(Sec::LDS_RUN)>> {
-    static constexpr bool value = Sec::LDS_RUN;
-};
-
-// Section count up to which a chain of this section type runs faster on the LDS-DMA kernel than on the register-window
-// kernel at the C2 shape, both at their worst output placement (tools/tune_lds.hip): i32 DF1 x3 0.77 vs 0.62, x4 0.61 vs
-// 0.68; wide x2 0.73 vs 0.65; f32 DF1 / DF2T x2 0.75-0.77 vs 0.60-0.69, x3 0.70 vs 0.71, x4 0.54-0.57 vs 0.57-0.62;
-// Normal x2 0.77-0.81 vs 0.66-0.70, x4 0.51 vs 0.53.
-template <class Sec, class = void>
-struct SecLdsMaxN {
-    static constexpr int value = 0;  // f64 sections: 8-byte samples never take the LDS-DMA kernel
-};
-template <class Sec>
-struct SecLdsMaxN<Sec, std::void_t<decltype(Sec::LDS_MAX_N)>> {
-    static constexpr int value = Sec::LDS_MAX_N;
-};
-
 // N independent sections in series (`[C] x [S]`, compose.rs:43-77).
-// largest number of sub-blocks per workgroup a single section is instantiated with on the sweep kernel: 16 (2^20 lanes in one sweep) for the
-// biquad sections proper, Sec::SWEEP_LPT for the others (Normal: 8)
-template <class Sec, class = void>
-struct SecSweepLpt {
-    static constexpr int value = 16;
-};
-template <class Sec>
-struct SecSweepLpt<Sec, std::void_t<decltype(Sec::SWEEP_LPT)>> {
-    static constexpr int value = Sec::SWEEP_LPT;
-};
-// sections whose single-section processors run 8 / 16 blocks per workgroup of the sweep kernel on its two-barrier schedule (fm_sweep.h)
-template <class Sec, class = void>
-struct SecBigTwoBarrier : std::false_type {};
-template <class Sec>
-struct SecBigTwoBarrier<Sec, std::void_t<decltype(Sec::SWEEP_BIG_TWO_BARRIER)>> : std::integral_constant<bool, Sec::SWEEP_BIG_TWO_BARRIER> {};
-// sections whose full blocks the sweep kernel runs WITHOUT the `s_sleep` pacing although they are cheap: the clamped ones and `Normal` (65536 lanes: f32 DF1 clamp
-// 0.67 of the peak paced, 0.76 unpaced; f32 DF2T clamp 0.69 / 0.75; i32 DF1 clamp 0.73 / 0.75; Normal f32 0.73 / 0.75 — the unclamped ones 0.77-0.80 / 0.76)
-template <class Sec, class = void>
-struct SecUnpaced : std::integral_constant<bool, Sec::kClamp> {};
-template <class Sec>
-struct SecUnpaced<Sec, std::void_t<decltype(Sec::SWEEP_UNPACED)>> : std::integral_constant<bool, Sec::SWEEP_UNPACED || Sec::kClamp> {};
-template <class Sec, class = void>
-struct SecHasTile : std::false_type {};
-template <class Sec>
-struct SecHasTile<Sec, std::void_t<decltype(Sec::HAS_TILE)>> : std::integral_constant<bool, Sec::HAS_TILE> {};
-
 template <class Sec, int N>
 struct Chain {
     using In = typename Sec::T;
@@ -486,12 +481,12 @@ struct Chain {
     static constexpr int LDS_WORDS = 0;
     static constexpr int IN_DIV = 1;
     static constexpr int COST = N * Sec::COST;
-    static constexpr int LDS_RING = N == 1 ? SecRing<Sec>::value : 4;  // N >= 2: tools/tune_lds.hip (worst placement 0.75-0.77 against 0.68 at 8 tiles for N = 2)
-    static constexpr bool LDS_RUN = N == 1 && SecRun<Sec>::value;
-    static constexpr bool LDS_ELIGIBLE = N <= SecLdsMaxN<Sec>::value;
-    static constexpr int SWEEP_MAX_LPT = N == 1 ? SecSweepLpt<Sec>::value : N == 2 ? 8 : 2;  // sub-blocks per workgroup on the sweep kernel (fm_sweep.h)
-    static constexpr bool SWEEP_BIG_TWO_BARRIER = N == 1 && SecBigTwoBarrier<Sec>::value;
-    static constexpr bool SWEEP_UNPACED = SecUnpaced<Sec>::value;
+    static constexpr int LDS_RING = N == 1 ? Sec::LDS_RING : 4;  // N >= 2: tools/tune_lds.hip (worst placement 0.75-0.77 against 0.68 at 8 tiles for N = 2)
+    static constexpr bool LDS_RUN = N == 1 && Sec::LDS_RUN;
+    static constexpr bool LDS_ELIGIBLE = N <= Sec::LDS_MAX_N;
+    static constexpr int SWEEP_MAX_LPT = N == 1 ? Sec::SWEEP_LPT : N == 2 ? 8 : 2;  // sub-blocks per workgroup on the sweep kernel (fm_sweep.h)
+    static constexpr bool SWEEP_BIG_TWO_BARRIER = N == 1 && Sec::SWEEP_BIG_TWO_BARRIER;
+    static constexpr bool SWEEP_UNPACED = Sec::SWEEP_UNPACED || Sec::kClamp;
     using Params = ChainParams<typename Sec::Sec, N>;
     uint32_t s[N][Sec::W];
 
@@ -516,7 +511,7 @@ struct Chain {
         return x;
     }
     // tile form of a single section that has one (Sec::tile; lane_stream.h: HasTileOf): `p` points at SB chains of independent lanes
-    static constexpr bool HAS_TILE = N == 1 && SecHasTile<Sec>::value;
+    static constexpr bool HAS_TILE = N == 1 && Sec::HAS_TILE;
     template <int SB, int R>
     static __device__ __forceinline__ void tile(const Params &prm, Chain *p, const In (&x)[SB * R], Out (&y)[SB * R])
     {
@@ -642,13 +637,13 @@ struct ChainByLane {
     static constexpr int LDS_WORDS = 0;
     static constexpr int IN_DIV = 1;
     static constexpr int COST = N * Sec::COST;
-    static constexpr int LDS_RING = N == 1 ? SecRing<Sec>::value : 4;  // N >= 2: tools/tune_lds.hip (worst placement 0.75-0.77 against 0.68 at 8 tiles for N = 2)
-    static constexpr bool LDS_RUN = N == 1 && SecRun<Sec>::value;
-    static constexpr bool LDS_ELIGIBLE = N <= SecLdsMaxN<Sec>::value;
+    static constexpr int LDS_RING = N == 1 ? Sec::LDS_RING : 4;  // N >= 2: tools/tune_lds.hip (worst placement 0.75-0.77 against 0.68 at 8 tiles for N = 2)
+    static constexpr bool LDS_RUN = N == 1 && Sec::LDS_RUN;
+    static constexpr bool LDS_ELIGIBLE = N <= Sec::LDS_MAX_N;
     static constexpr int CV = Sec::kClamp ? 8 : 5;
     // sub-blocks per workgroup on the sweep kernel (fm_sweep.h): every lane carries its own coefficients in registers beside its state
     static constexpr int SWEEP_MAX_LPT = N == 1 ? 8 : 2;
-    static constexpr bool SWEEP_BIG_TWO_BARRIER = N == 1 && SecBigTwoBarrier<Sec>::value && std::is_same<typename Sec::T, float>::value;  // (i32 DF1 by lane: one barrier)
+    static constexpr bool SWEEP_BIG_TWO_BARRIER = N == 1 && Sec::SWEEP_BIG_TWO_BARRIER && std::is_same<typename Sec::T, float>::value;  // (i32 DF1 by lane: one barrier)
     // never paced: with the coefficient registers the paced schedule is bimodal on some boxes (65536 lanes, i32 DF1 / f32 DF2T by lane: launches of 0.345 and of
     // 0.41-0.43 ms in one process, median 0.41; unpaced 0.35-0.36 every time; other boxes 0.34 paced)
     static constexpr bool SWEEP_UNPACED = true;
@@ -683,319 +678,42 @@ struct ChainByLane {
     }
 };
 
-// ------------------------------------------------------------ host dispatch
-// Row pitches of the `_pitch` entry points (include/idsp_hip.h): elements between the starts of consecutive lanes
-// (LANE_MAJOR) or consecutive frames (FRAME_MAJOR); 0 = dense.  A pitch must cover a row, and an in-place call must
-// use the same pitch on both sides.
-inline int check_pitch(const void *x, const void *y, size_t lanes, size_t frames, int layout, Pitch pitch)
-{
-    const size_t row = layout == IDSP_LANE_MAJOR ? frames : lanes;
-    if ((pitch.x && pitch.x < row) || (pitch.y && pitch.y < row))
-        return fail(IDSP_EINVAL, "pitch (%zu, %zu) shorter than a row of %zu elements", pitch.x, pitch.y, row);
-    if (x == y && (pitch.x ? pitch.x : row) != (pitch.y ? pitch.y : row))
-        return fail(IDSP_EINVAL, "in-place call with different x and y pitches (%zu, %zu)", pitch.x, pitch.y);
-    return IDSP_OK;
-}
 
-template <class T>
-int copy_through(const T *x, T *y, size_t lanes, size_t frames, int layout, hipStream_t s, Pitch pitch)
-{
-    if (x == y) return IDSP_OK;
-    const size_t row = layout == IDSP_LANE_MAJOR ? frames : lanes, rows = layout == IDSP_LANE_MAJOR ? lanes : frames;
-    const size_t xp = pitch.x ? pitch.x : row, yp = pitch.y ? pitch.y : row;
-    IDSP_HIP_TRY(hipMemcpy2DAsync(y, yp * sizeof(T), x, xp * sizeof(T), row * sizeof(T), rows, hipMemcpyDeviceToDevice, s));
-    return IDSP_OK;
-}
-
-template <class Sec, int N, class CfgFill>
-int run_chain_n(CfgFill fill, size_t first, void *state, const typename Sec::T *x, typename Sec::T *y,
-                size_t lanes, size_t frames, int layout, hipStream_t s, Pitch pitch = {})
-{
-    typename Chain<Sec, N>::Params prm;
-    for (int k = 0; k < N; k++) fill(prm.sec[k], first + k);
-    uint32_t *st = static_cast<uint32_t *>(state) + first * Sec::W * lanes;
-    return launch_stream<Chain<Sec, N>>(prm, st, x, y, lanes, frames, layout, s, pitch);
-}
-
-// Sections first .. first + NA + NB - 1 on the two-wave kernel: wave 0 runs Chain<Sec, NA>, wave 1 Chain<Sec, NB> one tile behind
-template <class Sec, int NA, int NB, class CfgFill>
-int run_chain_duo(CfgFill fill, size_t first, void *state, const typename Sec::T *x, typename Sec::T *y, size_t lanes, size_t frames,
-                  hipStream_t s, Pitch pitch)
-{
-    typename Chain<Sec, NA>::Params pa;
-    typename Chain<Sec, NB>::Params pb;
-    for (int k = 0; k < NA; k++) fill(pa.sec[k], first + k);
-    for (int k = 0; k < NB; k++) fill(pb.sec[k], first + NA + k);
-    uint32_t *st = static_cast<uint32_t *>(state) + first * Sec::W * lanes;
-    return launch_duo<Chain<Sec, NA>, Chain<Sec, NB>>(pa, pb, st, st + size_t(NA) * Sec::W * lanes, x, y, lanes, frames, s, pitch);
-}
-// section types that have the two-wave instantiations (4-byte samples)
-template <class Sec>
-struct DuoSec : std::integral_constant<bool, sizeof(typename Sec::T) == 4> {};
-constexpr int kMaxChainDuo = 8;
-
-// n sections in passes of <= kMaxChain (<= kMaxChainDuo on the two-wave kernel): the first pass reads x, later passes
-// run in place on y — literally the reference's slice composition.
-template <class Sec, class CfgFill>
-int run_chain(CfgFill fill, size_t n, void *state, const typename Sec::T *x, typename Sec::T *y,
-              size_t lanes, size_t frames, int layout, hipStream_t s, Pitch pitch = {})
-{
-    using T = typename Sec::T;
-    if (lanes == 0 || frames == 0) return IDSP_OK;
-    if (n == 0) return copy_through<T>(x, y, lanes, frames, layout, s, pitch);  // empty slice: y.copy_from_slice(x), compose.rs:63-65
-    size_t done = 0;
-    const T *src = x;
-    while (done < n) {
-        if constexpr (DuoSec<Sec>::value) {
-            const size_t md = n - done < size_t(kMaxChainDuo) ? n - done : size_t(kMaxChainDuo);
-            // (four sections: +9 % for plain i32 DF1, +20 % for the f32 forms, -1 % / -5 % for the clamp / wide forms, which stay)
-            if (duo_wanted(md, lanes, layout) && (md >= 5 || (!Sec::kClamp && Sec::W <= 4))) {
-                int rc;
-                switch (md) {
-                    case 4: rc = run_chain_duo<Sec, 2, 2>(fill, done, state, src, y, lanes, frames, s, pitch); break;
-                    case 5: rc = run_chain_duo<Sec, 3, 2>(fill, done, state, src, y, lanes, frames, s, pitch); break;
-                    case 6: rc = run_chain_duo<Sec, 3, 3>(fill, done, state, src, y, lanes, frames, s, pitch); break;
-                    case 7: rc = run_chain_duo<Sec, 4, 3>(fill, done, state, src, y, lanes, frames, s, pitch); break;
-                    default: rc = run_chain_duo<Sec, 4, 4>(fill, done, state, src, y, lanes, frames, s, pitch); break;
-                }
-                if (rc) return rc;
-                done += md;
-                src = y;
-                pitch.x = pitch.y;
-                continue;
-            }
-        }
-        const size_t m = n - done < size_t(kMaxChain) ? n - done : size_t(kMaxChain);
-        int rc;
-        switch (m) {
-            case 1: rc = run_chain_n<Sec, 1>(fill, done, state, src, y, lanes, frames, layout, s, pitch); break;
-            case 2: rc = run_chain_n<Sec, 2>(fill, done, state, src, y, lanes, frames, layout, s, pitch); break;
-            case 3: rc = run_chain_n<Sec, 3>(fill, done, state, src, y, lanes, frames, layout, s, pitch); break;
-            default: rc = run_chain_n<Sec, 4>(fill, done, state, src, y, lanes, frames, layout, s, pitch); break;
-        }
-        if (rc) return rc;
-        done += m;
-        src = y;
-        pitch.x = pitch.y;  // later passes run in place on y
-    }
-    return IDSP_OK;
-}
-
-inline int check_frac(int frac, size_t k)
-{
-    // `const { assert!(F >= 0 && F < 32) }` biquad.rs:448-450,513-515
-    if (frac < 0 || frac > 31) return fail(IDSP_EINVAL, "section %zu: frac = %d not in 0..31", k, frac);
-    return IDSP_OK;
-}
-
-constexpr int kMaxChainByLane = 2;  // coefficient registers come on top of the state
-
-// n per-lane sections in passes of <= kMaxChainByLane (stage-major like run_chain)
-template <class Sec>
-int run_chain_bylane(const void *coef, int frac, size_t n, void *state, const typename Sec::T *x, typename Sec::T *y,
-                     size_t lanes, size_t frames, int layout, hipStream_t s, Pitch pitch = {})
-{
-    using T = typename Sec::T;
-    if (lanes == 0 || frames == 0) return IDSP_OK;
-    if (n == 0) return copy_through<T>(x, y, lanes, frames, layout, s, pitch);
-    constexpr int CV = ChainByLane<Sec, 1>::CV;
-    size_t done = 0;
-    const T *src = x;
-    while (done < n) {
-        if constexpr (sizeof(T) == 4) {
-            // three or four sections of a bank in one pass on the two-wave kernel (two sections per wave; coefficient and state
-            // planes of the second wave start two sections further into the records)
-            const size_t md = n - done < size_t(2 * kMaxChainByLane) ? n - done : size_t(2 * kMaxChainByLane);
-            if (md >= 3 && duo_wanted(5, lanes, layout)) {
-                ByLaneParams pa{static_cast<const T *>(coef) + done * CV * lanes, frac}, pb{static_cast<const T *>(coef) + (done + 2) * CV * lanes, frac};
-                uint32_t *sa = static_cast<uint32_t *>(state) + done * Sec::W * lanes, *sb = sa + 2 * Sec::W * lanes;
-                const int rc = md == 3 ? launch_duo<ChainByLane<Sec, 2>, ChainByLane<Sec, 1>>(pa, pb, sa, sb, src, y, lanes, frames, s, pitch)
-                                       : launch_duo<ChainByLane<Sec, 2>, ChainByLane<Sec, 2>>(pa, pb, sa, sb, src, y, lanes, frames, s, pitch);
-                if (rc) return rc;
-                done += md;
-                src = y;
-                pitch.x = pitch.y;
-                continue;
-            }
-        }
-        const size_t m = n - done < size_t(kMaxChainByLane) ? n - done : size_t(kMaxChainByLane);
-        ByLaneParams prm{static_cast<const T *>(coef) + done * CV * lanes, frac};
-        uint32_t *st = static_cast<uint32_t *>(state) + done * Sec::W * lanes;
-        const int rc = m == 1 ? launch_stream<ChainByLane<Sec, 1>>(prm, st, src, y, lanes, frames, layout, s, pitch)
-                              : launch_stream<ChainByLane<Sec, 2>>(prm, st, src, y, lanes, frames, layout, s, pitch);
-        if (rc) return rc;
-        done += m;
-        src = y;
-        pitch.x = pitch.y;
-    }
-    return IDSP_OK;
-}
-
-template <class Sec>
-int entry_bylane(const void *coef, int frac, size_t n, void *state, const typename Sec::T *x, typename Sec::T *y,
-                 size_t lanes, size_t frames, int layout, void *stream, Pitch pitch = {})
-{
-    int rc = check_stream_args(coef, n, state, x, y, lanes, frames, layout);
-    if (rc) return rc;
-    if ((rc = check_pitch(x, y, lanes, frames, layout, pitch))) return rc;
-    if (std::is_same<typename Sec::T, int32_t>::value && (rc = check_frac(frac, 0))) return rc;
-    return run_chain_bylane<Sec>(coef, frac, n, state, x, y, lanes, frames, layout, as_stream(stream), pitch);
-}
-
-template <class T, int N, class CfgFill>
-int run_cascade_n(CfgFill fill, void *state, const T *x, T *y, size_t lanes, size_t frames, int layout, hipStream_t s, Pitch pitch)
-{
-    typename CascadeDf1<T, N>::Params prm;
-    for (int k = 0; k < N; k++) fill(prm.sec[k], size_t(k));
-    return launch_stream<CascadeDf1<T, N>>(prm, state, x, y, lanes, frames, layout, s, pitch);
-}
-
-// `Cascade` of NA + NB sections on the two-wave kernel.  Section k's input history is section k - 1's output history, so wave 1 is
-// the same processor type started 2 NA values into the state record: its "x history" is y[NA - 1]'s, which it keeps up to date
-// from the samples wave 0 hands over (both waves write that pair back: the same values).
-template <class T, int NA, int NB, class CfgFill>
-int run_cascade_duo(CfgFill fill, void *state, const T *x, T *y, size_t lanes, size_t frames, hipStream_t s, Pitch pitch)
-{
-    typename CascadeDf1<T, NA>::Params pa;
-    typename CascadeDf1<T, NB>::Params pb;
-    for (int k = 0; k < NA; k++) fill(pa.sec[k], size_t(k));
-    for (int k = 0; k < NB; k++) fill(pb.sec[k], size_t(NA + k));
-    uint32_t *st = static_cast<uint32_t *>(state);
-    return launch_duo<CascadeDf1<T, NA>, CascadeDf1<T, NB>>(pa, pb, st, st + size_t(2 * NA) * (sizeof(T) / 4) * lanes, x, y, lanes, frames, s, pitch);
-}
-
-template <class T, class CfgFill>
-int run_cascade(CfgFill fill, size_t n, void *state, const T *x, T *y, size_t lanes, size_t frames, int layout,
-                hipStream_t s, Pitch pitch = {})
-{
-    if (int rc = check_pitch(x, y, lanes, frames, layout, pitch)) return rc;
-    if (n < 1 || n > size_t(kMaxCascade)) return fail(IDSP_EINVAL, "cascade sections n = %zu not in 1..%d", n, kMaxCascade);
-    if (lanes == 0 || frames == 0) return IDSP_OK;
-    if constexpr (sizeof(T) == 4) {
-        if (n >= 5 && duo_wanted(n, lanes, layout)) {  // (4 sections stay on the LDS-DMA kernel: 0.69 against 0.62)
-            switch (n) {
-                case 5: return run_cascade_duo<T, 3, 2>(fill, state, x, y, lanes, frames, s, pitch);
-                case 6: return run_cascade_duo<T, 3, 3>(fill, state, x, y, lanes, frames, s, pitch);
-                case 7: return run_cascade_duo<T, 4, 3>(fill, state, x, y, lanes, frames, s, pitch);
-                default: return run_cascade_duo<T, 4, 4>(fill, state, x, y, lanes, frames, s, pitch);
-            }
-        }
-    }
-    switch (n) {
-        case 1: return run_cascade_n<T, 1>(fill, state, x, y, lanes, frames, layout, s, pitch);
-        case 2: return run_cascade_n<T, 2>(fill, state, x, y, lanes, frames, layout, s, pitch);
-        case 3: return run_cascade_n<T, 3>(fill, state, x, y, lanes, frames, layout, s, pitch);
-        case 4: return run_cascade_n<T, 4>(fill, state, x, y, lanes, frames, layout, s, pitch);
-        case 5: return run_cascade_n<T, 5>(fill, state, x, y, lanes, frames, layout, s, pitch);
-        case 6: return run_cascade_n<T, 6>(fill, state, x, y, lanes, frames, layout, s, pitch);
-        case 7: return run_cascade_n<T, 7>(fill, state, x, y, lanes, frames, layout, s, pitch);
-        default: return run_cascade_n<T, 8>(fill, state, x, y, lanes, frames, layout, s, pitch);
-    }
-}
-
-struct FillI32 {
-    const idsp_biquad_i32 *c;
-    void operator()(SecI32 &d, size_t k) const
-    {
-        for (int i = 0; i < 5; i++) d.ba[i] = c[k].ba[i];
-        d.frac = c[k].frac;
-        d.u = 0;
-        d.mn = INT32_MIN;
-        d.mx = INT32_MAX;
-    }
-};
-struct FillClampI32 {
-    const idsp_biquad_clamp_i32 *c;
-    void operator()(SecI32 &d, size_t k) const
-    {
-        for (int i = 0; i < 5; i++) d.ba[i] = c[k].ba[i];
-        d.frac = c[k].frac;
-        d.u = c[k].u;
-        d.mn = c[k].min;
-        d.mx = c[k].max;
-    }
-};
-struct FillF32 {
-    const idsp_biquad_f32 *c;
-    void operator()(SecF32 &d, size_t k) const
-    {
-        for (int i = 0; i < 5; i++) d.ba[i] = c[k].ba[i];
-        d.u = 0.f;
-        d.mn = -__builtin_inff();
-        d.mx = __builtin_inff();
-    }
-};
-struct FillClampF32 {
-    const idsp_biquad_clamp_f32 *c;
-    void operator()(SecF32 &d, size_t k) const
-    {
-        for (int i = 0; i < 5; i++) d.ba[i] = c[k].ba[i];
-        d.u = c[k].u;
-        d.mn = c[k].min;
-        d.mx = c[k].max;
-    }
-};
-
-struct FillF64 {
-    const idsp_biquad_f64 *c;
-    void operator()(SecF64 &d, size_t k) const
-    {
-        for (int i = 0; i < 5; i++) d.ba[i] = c[k].ba[i];
-        d.u = 0.0;
-        d.mn = -__builtin_inf();
-        d.mx = __builtin_inf();
-    }
-};
-struct FillClampF64 {
-    const idsp_biquad_clamp_f64 *c;
-    void operator()(SecF64 &d, size_t k) const
-    {
-        for (int i = 0; i < 5; i++) d.ba[i] = c[k].ba[i];
-        d.u = c[k].u;
-        d.mn = c[k].min;
-        d.mx = c[k].max;
-    }
-};
-
-template <class Sec, class Cfg, class Fill>
-int entry_i32(const Cfg *cfg, size_t n, void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames,
-              int layout, void *stream, Pitch pitch = {})
-{
-    int rc = check_stream_args(cfg, n, state, x, y, lanes, frames, layout);
-    if (rc) return rc;
-    if ((rc = check_pitch(x, y, lanes, frames, layout, pitch))) return rc;
-    for (size_t k = 0; k < n; k++)
-        if ((rc = check_frac(cfg[k].frac, k))) return rc;
-    return run_chain<Sec>(Fill{cfg}, n, state, x, y, lanes, frames, layout, as_stream(stream), pitch);
-}
-
-template <class Sec, class Cfg, class Fill>
-int entry_f64(const Cfg *cfg, size_t n, void *state, const double *x, double *y, size_t lanes, size_t frames,
-              int layout, void *stream, Pitch pitch = {})
-{
-    int rc = check_stream_args(cfg, n, state, x, y, lanes, frames, layout);
-    if (rc) return rc;
-    if ((rc = check_pitch(x, y, lanes, frames, layout, pitch))) return rc;
-    return run_chain<Sec>(Fill{cfg}, n, state, x, y, lanes, frames, layout, as_stream(stream), pitch);
-}
-
-template <class Sec, class Cfg, class Fill>
-int entry_f32(const Cfg *cfg, size_t n, void *state, const float *x, float *y, size_t lanes, size_t frames,
-              int layout, void *stream, Pitch pitch = {})
-{
-    int rc = check_stream_args(cfg, n, state, x, y, lanes, frames, layout);
-    if (rc) return rc;
-    if ((rc = check_pitch(x, y, lanes, frames, layout, pitch))) return rc;
-    return run_chain<Sec>(Fill{cfg}, n, state, x, y, lanes, frames, layout, as_stream(stream), pitch);
-}
+// What `Chain` (N = 1 .. 4) and `ChainByLane` (N = 1, 2; not Normal) make of every section type they are instantiated with: the values the launcher
+// reads (lane_stream.h, fm_sweep.h), written out by hand so that a default of SecDefaults or a shadowing member cannot move one unseen.
+//   ring / run: LDS_RING, LDS_RUN of one section (N >= 2: 4, false)    maxn: LDS_ELIGIBLE = N <= maxn    tile: HAS_TILE of one section
+//   lpt: SWEEP_MAX_LPT of one section (Chain N = 2: 8, N >= 3: 2; ChainByLane: 8, 2)
+//   two: SWEEP_BIG_TWO_BARRIER of one section (ChainByLane: f32 only)  unpaced: SWEEP_UNPACED (ChainByLane: always)
+template <class P, int N, int RING, bool RUN, int MAXN, int LPT, bool TWO, bool UNPACED>
+constexpr bool chain_is = P::LDS_RING == (N == 1 ? RING : 4) && P::LDS_RUN == (N == 1 && RUN) && P::LDS_ELIGIBLE == (N <= MAXN) && P::SWEEP_MAX_LPT == LPT &&
+                          P::SWEEP_BIG_TWO_BARRIER == (N == 1 && TWO) && P::SWEEP_UNPACED == UNPACED;
+#define IDSP_CHAIN_IS(SEC, RING, RUN, MAXN, LPT, TWO, UNPACED, TILE, BYLANE, TWO_BYLANE)                                                                      \
+    static_assert(chain_is<Chain<SEC, 1>, 1, RING, RUN, MAXN, LPT, TWO, UNPACED> && chain_is<Chain<SEC, 2>, 2, RING, RUN, MAXN, 8, TWO, UNPACED> &&           \
+                      chain_is<Chain<SEC, 3>, 3, RING, RUN, MAXN, 2, TWO, UNPACED> && chain_is<Chain<SEC, 4>, 4, RING, RUN, MAXN, 2, TWO, UNPACED> &&         \
+                      Chain<SEC, 1>::HAS_TILE == TILE && !Chain<SEC, 2>::HAS_TILE && !Chain<SEC, 3>::HAS_TILE && !Chain<SEC, 4>::HAS_TILE,                   \
+                  "Chain<" #SEC ", N>");                                                                                                                     \
+    static_assert(!BYLANE || (chain_is<ChainByLane<SEC, 1>, 1, RING, RUN, MAXN, 8, TWO_BYLANE, true> &&                                                      \
+                              chain_is<ChainByLane<SEC, 2>, 2, RING, RUN, MAXN, 2, TWO_BYLANE, true>),                                                       \
+                  "ChainByLane<" #SEC ", N>");
+//            section          ring run  maxn lpt two    unpaced tile  | by lane: two
+IDSP_CHAIN_IS(Df1I32<false>,    7, false, 3, 16, true,  false, true,   true, false)
+IDSP_CHAIN_IS(Df1I32<true>,     4, false, 3, 16, false, true,  true,   true, false)
+IDSP_CHAIN_IS(DitherI32<false>, 7, false, 2, 16, false, false, false,  true, false)
+IDSP_CHAIN_IS(DitherI32<true>,  4, false, 2, 16, false, true,  false,  true, false)
+IDSP_CHAIN_IS(WideI32<false>,   5, true,  2, 16, false, false, false,  true, false)
+IDSP_CHAIN_IS(WideI32<true>,    4, false, 2, 16, false, true,  false,  true, false)
+IDSP_CHAIN_IS(Df1F32<false>,    5, false, 2, 16, false, false, false,  true, false)
+IDSP_CHAIN_IS(Df1F32<true>,     4, false, 2, 16, false, true,  false,  true, false)
+IDSP_CHAIN_IS(Df2tF32<false>,   7, false, 2, 16, true,  false, false,  true, true)
+IDSP_CHAIN_IS(Df2tF32<true>,    4, false, 2, 16, false, true,  false,  true, false)
+IDSP_CHAIN_IS(Df1F64<false>,    8, false, 0, 16, false, false, false,  true, false)
+IDSP_CHAIN_IS(Df1F64<true>,     8, false, 0, 16, false, true,  false,  true, false)
+IDSP_CHAIN_IS(Df2tF64<false>,   8, false, 0, 16, false, false, false,  true, false)
+IDSP_CHAIN_IS(Df2tF64<true>,    8, false, 0, 16, false, true,  false,  true, false)
+IDSP_CHAIN_IS(NormalI32,        5, true,  2, 8,  false, false, false,  false, false)
+IDSP_CHAIN_IS(NormalF32,        5, true,  2, 8,  true,  true,  false,  false, false)
+IDSP_CHAIN_IS(NormalF64,        8, false, 0, 16, false, false, false,  false, false)
+#undef IDSP_CHAIN_IS
 
 }  // namespace bq
 }  // namespace idsp
-
-// `<entry>_pitch` twin of a shared-coefficient entry point (include/idsp_hip.h): same call with explicit row pitches.
-#define IDSP_PITCH_TWIN(name, Cfg, T, ENTRY, ...)                                                                      \
-    int name##_pitch(const Cfg *cfg, size_t n, void *state, const T *x, size_t x_pitch, T *y, size_t y_pitch,          \
-                     size_t lanes, size_t frames, int layout, void *stream)                                            \
-    {                                                                                                                  \
-        return ENTRY<__VA_ARGS__>(cfg, n, state, x, y, lanes, frames, layout, stream, ::idsp::Pitch{x_pitch, y_pitch}); \
-    }

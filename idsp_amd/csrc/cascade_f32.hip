@@ -1,5 +1,5 @@
-// cascade_f32.hip — C-ABI entry points (include/idsp_hip.h) of the f32 cascade with shared delay lines; device code in biquad_sections.h.
-#include "biquad_sections.h"
+// cascade_f32.hip — C-ABI entry points (include/idsp_hip.h) of the f32 cascade with shared delay lines; device code in biquad_sections.h, host side in biquad_host.h.
+#include "biquad_host.h"
 
 using namespace idsp;
 using namespace idsp::bq;
@@ -11,7 +11,7 @@ int idsp_cascade_f32_df1(const idsp_biquad_f32 *cfg, size_t n, void *state, cons
 {
     int rc = check_stream_args(cfg, n, state, x, y, lanes, frames, layout);
     if (rc) return rc;
-    return run_cascade<float>(FillF32{cfg}, n, state, x, y, lanes, frames, layout, as_stream(stream));
+    return run_cascade<float>(Fill{cfg}, n, state, x, y, lanes, frames, layout, as_stream(stream));
 }
 
 // explicit row pitches (include/idsp_hip.h, "_pitch" entries)
@@ -20,7 +20,7 @@ int idsp_cascade_f32_df1_pitch(const idsp_biquad_f32 *cfg, size_t n, void *state
 {
     int rc = check_stream_args(cfg, n, state, x, y, lanes, frames, layout);
     if (rc) return rc;
-    return run_cascade<float>(FillF32{cfg}, n, state, x, y, lanes, frames, layout, as_stream(stream), Pitch{x_pitch, y_pitch});
+    return run_cascade<float>(Fill{cfg}, n, state, x, y, lanes, frames, layout, as_stream(stream), Pitch{x_pitch, y_pitch});
 }
 
 }  // extern "C"

@@ -343,7 +343,7 @@ int idsp_fm_disc_i32(const idsp_fm_disc *cfg, void *state, const int32_t *x, int
     if (lanes == 0 || frames == 0) return IDSP_OK;
     FmDiscProc::Params p;
     p.carrier = cfg->carrier;
-    bq::FillI32{&cfg->deemph}(p.sec, 0);
+    bq::Fill{&cfg->deemph}(p.sec, 0);
     FmDiscCall call;
     call.lanes = lanes, call.frames = frames, call.layout = layout;
     call.x = reinterpret_cast<uintptr_t>(x), call.y = reinterpret_cast<uintptr_t>(y);

@@ -207,10 +207,10 @@ template <int NS>
 int run_biquad_phase(const idsp_biquad_i32 *sec, void *state, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout, hipStream_t s, size_t pitch)
 {
     typename LockinBiquadProc<NS>::Params p;
-    bq::fill_sections(bq::FillI32{sec}, p.sec);
+    bq::fill_sections(bq::Fill{sec}, p.sec);
     return launch_stream<LockinBiquadProc<NS>>(p, state, x, reinterpret_cast<Cplx *>(y), lanes, frames, layout, s, Pitch{pitch, pitch});
 }
-// Sec = Df1I32<false> with FillI32 and T = int32_t, or Df1F32<false> with FillF32 and T = float
+// Sec = Df1I32<false> with Fill<idsp_biquad_i32> and T = int32_t, or Df1F32<false> with Fill<idsp_biquad_f32> and T = float
 template <class Sec, int NS, class Fill, class T>
 int run_biquad_lo(const Fill &fill, void *state, const T *x, const T *lo, T *y, size_t lanes, size_t frames, int layout, hipStream_t s, size_t pitch)
 {
@@ -317,7 +317,7 @@ int idsp_lockin_i32_biquad_lo_process(const idsp_biquad_i32 *sections, size_t n,
     for (size_t k = 0; k < n; k++)
         if (sections[k].frac < 0 || sections[k].frac > 31) return fail(IDSP_EINVAL, "section %zu: frac = %d not in 0..31", k, sections[k].frac);
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    return lockin_biquad_lo<bq::Df1I32<false>, bq::FillI32>(lockin_waves_biquad_lo, sections, n, state, x, lo, y, lanes, frames, layout, stream);
+    return lockin_biquad_lo<bq::Df1I32<false>, bq::Fill<idsp_biquad_i32>>(lockin_waves_biquad_lo, sections, n, state, x, lo, y, lanes, frames, layout, stream);
 }
 
 int idsp_lockin_f32_biquad_lo_process(const idsp_biquad_f32 *sections, size_t n, void *state, const float *x, const float *lo, float *y,
@@ -327,7 +327,7 @@ int idsp_lockin_f32_biquad_lo_process(const idsp_biquad_f32 *sections, size_t n,
     int rc = check_lo_args(sections, state, x, lo, y, lanes, frames, layout);
     if (rc) return rc;
     if (lanes == 0 || frames == 0) return IDSP_OK;
-    return lockin_biquad_lo<bq::Df1F32<false>, bq::FillF32>(lockin_waves_biquad_lo_f32, sections, n, state, x, lo, y, lanes, frames, layout, stream);
+    return lockin_biquad_lo<bq::Df1F32<false>, bq::Fill<idsp_biquad_f32>>(lockin_waves_biquad_lo_f32, sections, n, state, x, lo, y, lanes, frames, layout, stream);
 }
 
 }  // extern "C"

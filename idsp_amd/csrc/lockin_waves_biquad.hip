@@ -67,17 +67,17 @@ int run(size_t n, const Fill &fill, void *state, const void *x, const void *lo, 
 int lockin_waves_biquad_iq(const idsp_biquad_i32 *sec, size_t n, void *state, const int32_t *x, int32_t *y, size_t lanes, const LockinPlan &plan, hipStream_t s,
                            size_t pitch)
 {
-    return run<BqBank>(n, bq::FillI32{sec}, state, x, nullptr, y, lanes, plan, s, pitch);
+    return run<BqBank>(n, bq::Fill{sec}, state, x, nullptr, y, lanes, plan, s, pitch);
 }
 int lockin_waves_biquad_lo(const idsp_biquad_i32 *sec, size_t n, void *state, const int32_t *x, const int32_t *lo, int32_t *y, size_t lanes,
                            const LockinPlan &plan, hipStream_t s, size_t pitch)
 {
-    return run<BqLoBank>(n, bq::FillI32{sec}, state, x, lo, y, lanes, plan, s, pitch);
+    return run<BqLoBank>(n, bq::Fill{sec}, state, x, lo, y, lanes, plan, s, pitch);
 }
 int lockin_waves_biquad_lo_f32(const idsp_biquad_f32 *sec, size_t n, void *state, const float *x, const float *lo, float *y, size_t lanes,
                                const LockinPlan &plan, hipStream_t s, size_t pitch)
 {
-    return run<BqLoBankF32>(n, bq::FillF32{sec}, state, x, lo, y, lanes, plan, s, pitch);
+    return run<BqLoBankF32>(n, bq::Fill{sec}, state, x, lo, y, lanes, plan, s, pitch);
 }
 
 }  // namespace idsp

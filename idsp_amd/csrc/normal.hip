@@ -1,8 +1,8 @@
 // normal.hip — C-ABI entry points (include/idsp_hip.h) of `iir::normal::Normal` (src/iir/normal.rs:37-58); device code in
-// biquad_sections.h.
+// biquad_sections.h, host side in biquad_host.h.
 #include <cmath>
 
-#include "biquad_sections.h"
+#include "biquad_host.h"
 
 using namespace idsp;
 using namespace idsp::bq;
@@ -12,19 +12,19 @@ extern "C" {
 int idsp_normal_i32_df1(const idsp_biquad_i32 *cfg, size_t n, void *state, const int32_t *x, int32_t *y, size_t lanes,
                         size_t frames, int layout, void *stream)
 {
-    return entry_i32<NormalI32, idsp_biquad_i32, FillI32>(cfg, n, state, x, y, lanes, frames, layout, stream);
+    return entry_chain<NormalI32, idsp_biquad_i32, Fill<idsp_biquad_i32>>(cfg, n, state, x, y, lanes, frames, layout, stream);
 }
 
 int idsp_normal_f32_df1(const idsp_biquad_f32 *cfg, size_t n, void *state, const float *x, float *y, size_t lanes,
                         size_t frames, int layout, void *stream)
 {
-    return entry_f32<NormalF32, idsp_biquad_f32, FillF32>(cfg, n, state, x, y, lanes, frames, layout, stream);
+    return entry_chain<NormalF32, idsp_biquad_f32, Fill<idsp_biquad_f32>>(cfg, n, state, x, y, lanes, frames, layout, stream);
 }
 
 int idsp_normal_f64_df1(const idsp_biquad_f64 *cfg, size_t n, void *state, const double *x, double *y, size_t lanes,
                         size_t frames, int layout, void *stream)
 {
-    return entry_f64<NormalF64, idsp_biquad_f64, FillF64>(cfg, n, state, x, y, lanes, frames, layout, stream);
+    return entry_chain<NormalF64, idsp_biquad_f64, Fill<idsp_biquad_f64>>(cfg, n, state, x, y, lanes, frames, layout, stream);
 }
 
 int idsp_normal_from_sos(const double sos[6], double out[5])

@@ -2,13 +2,14 @@
 // (`iir::normal::Normal`: normal.hip — a translation unit of its own for the parallel build.)
 #include <cmath>
 
+#include "biquad_pass_plan.h"
 #include "biquad_sections.h"
 
 namespace idsp {
 namespace {
 
 // ------------------------------------------------------------------- Wdf
-constexpr int kWdfMaxSections = 4;  // sections fused per launch; longer chains run in passes
+// (kWdfMaxSections sections fused per launch; longer chains run in passes: biquad_pass_plan.h)
 
 // `i32 * Q32<32>` (dsp-fixedpoint/src/lib.rs:449-456)
 __device__ __forceinline__ int32_t mulq32(int32_t c, int32_t a) { return int32_t((int64_t(c) * int64_t(a)) >> 32); }
@@ -116,18 +117,6 @@ int wdf_cfg_check(const idsp_wdf *c, size_t n)
 }
 
 template <int K, int NMAX>
-int wdf_launch_n(const idsp_wdf *c, uint32_t *st, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout, hipStream_t s)
-{
-    WdfParamsT<NMAX> p{};
-    for (int k = 0; k < K; k++) {
-        p.n[k] = c[k].n;
-        uint32_t m = c[k].m;
-        for (int i = 0; i < NMAX; i++, m >>= 4) p.ad[k][i] = i < c[k].n ? adaptor_of(m & 0xf, c[k].a[i]) : adaptor_of(0, 0);
-    }
-    return launch_stream<WdfChain<K, NMAX>>(p, st, x, y, lanes, frames, layout, s);
-}
-
-template <int K, int NMAX>
 WdfParamsT<NMAX> wdf_params(const idsp_wdf *c)
 {
     WdfParamsT<NMAX> p{};
@@ -139,41 +128,31 @@ WdfParamsT<NMAX> wdf_params(const idsp_wdf *c)
     return p;
 }
 
-// K sections over two waves per 64 lanes (lane_stream.h, stream_frame_major_duo): the first KA on wave 0, the rest on wave 1,
-// whose state planes start behind the first KA sections' words.  ~80 VALU instructions per sample for the 7th-order chain of the
-// reference's embedded bench: 0.81 -> 0.70 ms at 65536 lanes x 4096 frames (profiles/r03_wdf_duo.log).
+// KA + KB sections of orders up to NMAX in one launch.  KB != 0: over two waves per 64 lanes (lane_stream.h, stream_frame_major_duo), the
+// first KA on wave 0, the rest on wave 1, whose state planes start behind the first KA sections' words.  ~80 VALU instructions per sample
+// for the 7th-order chain of the reference's embedded bench: 0.81 -> 0.70 ms at 65536 lanes x 4096 frames (profiles/r03_wdf_duo.log).
 template <int KA, int KB, int NMAX>
-int wdf_launch_duo_n(const idsp_wdf *c, uint32_t *st, const int32_t *x, int32_t *y, size_t lanes, size_t frames, hipStream_t s)
+int wdf_launch_n(const idsp_wdf *c, uint32_t *st, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout, hipStream_t s)
 {
-    size_t wa = 0;
-    for (int k = 0; k < KA; k++) wa += size_t(c[k].n);
-    return launch_duo<WdfChain<KA, NMAX>, WdfChain<KB, NMAX>>(wdf_params<KA, NMAX>(c), wdf_params<KB, NMAX>(c + KA), st, st + wa * lanes, x, y, lanes, frames, s,
-                                                               Pitch{});
-}
-template <int KA, int KB>
-int wdf_launch_duo(const idsp_wdf *c, uint32_t *st, const int32_t *x, int32_t *y, size_t lanes, size_t frames, hipStream_t s)
-{
-    int nmax = 0;
-    for (int k = 0; k < KA + KB; k++) nmax = c[k].n > nmax ? c[k].n : nmax;
-    if (nmax <= 2) return wdf_launch_duo_n<KA, KB, 2>(c, st, x, y, lanes, frames, s);
-    if (nmax <= 4) return wdf_launch_duo_n<KA, KB, 4>(c, st, x, y, lanes, frames, s);
-    return 1;  // sections of order 5 .. 8: the two-wave form would index its state through scratch; the caller keeps one wave
+    if constexpr (KB == 0) {
+        return launch_stream<WdfChain<KA, NMAX>>(wdf_params<KA, NMAX>(c), st, x, y, lanes, frames, layout, s);
+    } else {
+        size_t wa = 0;
+        for (int k = 0; k < KA; k++) wa += size_t(c[k].n);
+        return launch_duo<WdfChain<KA, NMAX>, WdfChain<KB, NMAX>>(wdf_params<KA, NMAX>(c), wdf_params<KB, NMAX>(c + KA), st, st + wa * lanes, x, y, lanes, frames,
+                                                                   s, Pitch{});
+    }
 }
 
-template <int K>
-int wdf_launch(const idsp_wdf *c, uint32_t *st, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout, hipStream_t s)
+// A pass whose largest order is `nmax`.  The two-wave form of orders 5 .. 8 would index its state through scratch: the caller keeps
+// such a pass on one wave (KB == 0).
+template <int KA, int KB>
+int wdf_launch(int nmax, const idsp_wdf *c, uint32_t *st, const int32_t *x, int32_t *y, size_t lanes, size_t frames, int layout, hipStream_t s)
 {
-    if constexpr (K >= 2) {
-        if (duo_wanted(5, lanes, layout)) {
-            const int rc = wdf_launch_duo<(K + 1) / 2, K / 2>(c, st, x, y, lanes, frames, s);
-            if (rc <= 0) return rc;
-        }
-    }
-    int nmax = 0;
-    for (int k = 0; k < K; k++) nmax = c[k].n > nmax ? c[k].n : nmax;
-    if (nmax <= 2) return wdf_launch_n<K, 2>(c, st, x, y, lanes, frames, layout, s);
-    if (nmax <= 4) return wdf_launch_n<K, 4>(c, st, x, y, lanes, frames, layout, s);
-    return wdf_launch_n<K, IDSP_WDF_MAX_ORDER>(c, st, x, y, lanes, frames, layout, s);
+    if (nmax <= 2) return wdf_launch_n<KA, KB, 2>(c, st, x, y, lanes, frames, layout, s);
+    if (nmax <= 4) return wdf_launch_n<KA, KB, 4>(c, st, x, y, lanes, frames, layout, s);
+    if constexpr (KB == 0) return wdf_launch_n<KA, 0, IDSP_WDF_MAX_ORDER>(c, st, x, y, lanes, frames, layout, s);
+    return fail(IDSP_EINVAL, "internal: a two-wave Wdf pass of order %d", nmax);
 }
 
 }  // namespace
@@ -231,13 +210,20 @@ int idsp_wdf_i32(const idsp_wdf *cfg, size_t n, void *state, const int32_t *x, i
     uint32_t *st = static_cast<uint32_t *>(state);
     const int32_t *src = x;
     size_t done = 0;
-    while (done < n) {  // stage-major passes like run_chain
-        const size_t k = n - done < size_t(kWdfMaxSections) ? n - done : size_t(kWdfMaxSections);
-        switch (k) {
-            case 1: rc = wdf_launch<1>(cfg + done, st, src, y, lanes, frames, layout, s); break;
-            case 2: rc = wdf_launch<2>(cfg + done, st, src, y, lanes, frames, layout, s); break;
-            case 3: rc = wdf_launch<3>(cfg + done, st, src, y, lanes, frames, layout, s); break;
-            default: rc = wdf_launch<4>(cfg + done, st, src, y, lanes, frames, layout, s); break;
+    while (done < n) {  // stage-major passes like run_chain (biquad_host.h)
+        Pass p = next_pass(wdf_rules(), n - done, lanes, layout, stream_switches());
+        const size_t k = size_t(p.na + p.nb);
+        int nmax = 0;
+        for (size_t j = 0; j < k; j++) nmax = cfg[done + j].n > nmax ? cfg[done + j].n : nmax;
+        if (nmax > 4) p = Pass{int(k), 0};  // orders 5 .. 8: one wave
+        switch (10 * p.na + p.nb) {
+            case 11: rc = wdf_launch<1, 1>(nmax, cfg + done, st, src, y, lanes, frames, layout, s); break;
+            case 21: rc = wdf_launch<2, 1>(nmax, cfg + done, st, src, y, lanes, frames, layout, s); break;
+            case 22: rc = wdf_launch<2, 2>(nmax, cfg + done, st, src, y, lanes, frames, layout, s); break;
+            case 10: rc = wdf_launch<1, 0>(nmax, cfg + done, st, src, y, lanes, frames, layout, s); break;
+            case 20: rc = wdf_launch<2, 0>(nmax, cfg + done, st, src, y, lanes, frames, layout, s); break;
+            case 30: rc = wdf_launch<3, 0>(nmax, cfg + done, st, src, y, lanes, frames, layout, s); break;
+            default: rc = wdf_launch<4, 0>(nmax, cfg + done, st, src, y, lanes, frames, layout, s); break;
         }
         if (rc) return rc;
         for (size_t j = 0; j < k; j++) st += size_t(cfg[done + j].n) * lanes;

@@ -22,6 +22,10 @@
 //           (fm_disc_plan_name), a tab, `form= waves= grid= body= tail= skew= shift= mod=`
 //   dds <lanes> <frames> <FM|LM> [IDSP_SWITCH=value ...]
 //        -> `plan_dds` for a call of idsp_dds_i32: `stream_<Processor>`, a tab, `split= circle=`
+//   passes <chain|bylane|cascade|wdf|i16> <sample bytes> <clamp 0|1> <state words> <n> <lanes> <FM|LM> [IDSP_SWITCH=value ...]
+//        -> `next_pass` (idsp_amd/csrc/biquad_pass_plan.h) until the n sections of a call are done: the launches in order, `na+nb` for one of the
+//           two-wave kernel and `na` for one of launch_stream, e.g. `4+4 2+2` or `4 4 1` (bytes, clamp and words are read by the families whose
+//           rules take them)
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -29,6 +33,7 @@
 #include <sstream>
 #include <string>
 
+#include "../../idsp_amd/csrc/biquad_pass_plan.h"
 #include "../../idsp_amd/csrc/lockin_plan.h"
 #include "../../idsp_amd/csrc/readout_plan.h"
 #include "../../idsp_amd/csrc/resample_plan.h"
@@ -228,6 +233,28 @@ int main()
             in >> m >> lanes >> layout;
             while (in >> word) env[word.substr(0, word.find('='))] = word.find('=') == std::string::npos ? "" : word.substr(word.find('=') + 1);
             printf("%d\n", int(duo_wanted(m, lanes, layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR, read_stream_switches(getenv_))));
+        } else if (cmd == "passes") {
+            std::string family, layout;
+            size_t bytes = 0, n = 0, lanes = 0;
+            int clamp = 0, words = 0;
+            in >> family >> bytes >> clamp >> words >> n >> lanes >> layout;
+            static const std::map<std::string, int> kFamilies = {{"chain", 0}, {"bylane", 1}, {"cascade", 2}, {"wdf", 3}, {"i16", 4}};
+            if (!in || !kFamilies.count(family) || (layout != "FM" && layout != "LM")) {
+                printf("error: %s\n", line.c_str());
+                continue;
+            }
+            while (in >> word) env[word.substr(0, word.find('='))] = word.find('=') == std::string::npos ? "" : word.substr(word.find('=') + 1);
+            const PassRules rules[5] = {chain_rules(bytes, clamp != 0, words), bylane_rules(bytes), cascade_rules(bytes), wdf_rules(), i16_rules()};
+            const PassRules &r = rules[kFamilies.at(family)];
+            const StreamSwitches sw = read_stream_switches(getenv_);
+            std::string out;
+            for (size_t done = 0; done < n;) {
+                const Pass p = next_pass(r, n - done, lanes, layout == "LM" ? IDSP_LANE_MAJOR : IDSP_FRAME_MAJOR, sw);
+                if (p.na + p.nb <= 0) break;  // (no rule does that: the line would not end)
+                out += (done ? " " : "") + std::to_string(p.na) + (p.nb ? "+" + std::to_string(p.nb) : "");
+                done += size_t(p.na + p.nb);
+            }
+            printf("%s\n", out.c_str());
         } else if (cmd == "lockin") {
             std::string entry, rest, out;
             in >> entry;

@@ -308,7 +308,7 @@ def test_pitch_twin_of_a_bylane_entry(gpu, layout):
 @pytest.mark.parametrize("what", ["wdf_i32 x 6", "cascade_f32_df1 x 8", "biquad_f32_df1 x 6"])
 def test_chains_in_place(gpu, what):
     """300 lanes x 200 frames, in place, both layouts: six Wdf sections and six biquad sections are two passes (four, then two in place
-    on y); a `Cascade` is one launch whatever its length (1 .. 8 sections, idsp_amd/csrc/biquad_sections.h `run_cascade`), so its longest
+    on y); a `Cascade` is one launch whatever its length (1 .. 8 sections, idsp_amd/csrc/biquad_host.h `run_cascade`), so its longest
     stands here."""
     from tests import _nw_cases as W
     from tests._backends import GpuBackend, OracleBackend
